@@ -84,7 +84,13 @@ def parse():
     ap.add_argument("--no-pmc", action="store_true", help="do not start the rocprofv3 --pmc child passes that measure `roofline.traffic` "
                     "(HBM bytes of the dominant kernel, FETCH_SIZE / WRITE_SIZE)")
     ap.add_argument("--dry-run", action="store_true", help="launch / rendezvous / timing protocol only, no GPU work (CPU test of --gpus N)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left a caller of map() (raw Gaussian parameters, "
+                         "window visibility, exposure and pose deltas of every keyframe) as DIR/<name>.npy, at most 64 MB in all")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def relaunch(args):
@@ -598,6 +604,8 @@ def main():
         lib.sgr_profile_enable((1 << len(KINDS)) - 1)
     elapsed, host_issue = B.timed(loop, args.steps)
     trace("timed loop done")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(loop, args.dump_outputs)
     kernel_ms = None
     if args.profile_all:
         ms, cnt = (C.c_float * len(KINDS))(), (C.c_int64 * len(KINDS))()
@@ -767,6 +775,45 @@ def main():
         print(json.dumps(out))
     if B.dist is not None:
         B.dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(loop, out_dir, budget=DUMP_BUDGET_BYTES, seed=0):
+    """What the timed path hands its caller after the last timed step, as float32 .npy files under `out_dir`: the raw Gaussian
+    parameters (the optimiser's tensors), occ_aware_visibility of the window (one row per window keyframe, 0 / 1), and per keyframe
+    (uid order) exposure a, b and the pose deltas.  Per-Gaussian arrays share one row set: all rows when they fit in `budget`,
+    otherwise a fixed seeded sample whose row indices are written as gaussian_rows.npy (float64)."""
+    import numpy as np
+    gm = loop.gaussians
+    n = gm._xyz.shape[0]
+    per_gaussian = {"xyz": gm._xyz, "f_dc": gm._features_dc, "f_rest": gm._features_rest, "opacity": gm._opacity,
+                    "scaling": gm._scaling, "rotation": gm._rotation}
+    per_gaussian = {"gaussians_" + k: v.detach().reshape(n, -1) for k, v in per_gaussian.items() if v.numel() > 0}
+    window = [kf for kf in loop.current_window if kf in loop.occ_aware_visibility]
+    if window:
+        per_gaussian["occ_aware_visibility"] = torch.stack([loop.occ_aware_visibility[kf].reshape(n) for kf in window], 1)
+    cams = [loop.viewpoints[uid] for uid in sorted(loop.viewpoints)]
+
+    def vec(t, k):
+        return torch.zeros(k) if t is None else t.detach().reshape(k).float().cpu()
+
+    small = {"keyframe_uids": torch.tensor([float(c.uid) for c in cams], dtype=torch.float64),
+             "keyframe_exposure_ab": torch.stack([torch.cat([vec(c.exposure_a, 1), vec(c.exposure_b, 1)]) for c in cams]),
+             "keyframe_pose_deltas": torch.stack([torch.cat([vec(c.cam_rot_delta, 3), vec(c.cam_trans_delta, 3)]) for c in cams])}
+    row_bytes = 4 * sum(v.shape[1] for v in per_gaussian.values())
+    room = budget - 4096 - sum(v.numel() * 8 for v in small.values())        # (4096: the .npy headers)
+    if n * row_bytes > room:
+        k = room // (row_bytes + 8)           # (+ 8: the float64 row index written beside the sample)
+        rows = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+        small["gaussian_rows"] = rows.double()
+        per_gaussian = {name: v[rows.to(v.device)] for name, v in per_gaussian.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in per_gaussian.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v.float().cpu().numpy())
+    for name, v in small.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v.cpu().numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32))
 
 
 def usable_cores():
