@@ -12,13 +12,16 @@ why = collections.Counter()
 orig = FusedMappingLoop._map_view
 def spy(self, cam, initialization=False, images=True, slot=False):
     vb = self._view(cam)
-    key = (cam._version, self._cap, id(cam.exposure_a), id(cam.original_image), vb.gt_depth.data_ptr(), initialization, self.keyframe_optimizers is not None)
+    row = self._exp.row_of(cam) if self._exp is not None else None          # (the key _map_view builds)
+    key = (cam._version, self._cap, cam.exposure_a.data_ptr(), cam.exposure_b.data_ptr(), cam.original_image.data_ptr(),
+           vb.gt_depth.data_ptr(), initialization, self.keyframe_optimizers is not None,
+           None if row is None else self._exp.grad.data_ptr() + 8 * row)
     hit = (vb.mv or {}).get((images, slot))
     if vb.mv is None: why["mv None"] += 1
     elif hit is None: why["no entry"] += 1
-    elif hit[0] != key:
-        names = ["version", "cap", "exp_a id", "image id", "gt_depth ptr", "init", "kfopt"]
-        why["key: " + ",".join(n for n, a, b in zip(names, hit[0], key) if a != b)] += 1
+    elif hit.key != key:
+        names = ["version", "cap", "exp_a ptr", "exp_b ptr", "image ptr", "gt_depth ptr", "init", "kfopt", "exp grad row"]
+        why["key: " + ",".join(n for n, a, b in zip(names, hit.key, key) if a != b)] += 1
     else: why["hit"] += 1
     return orig(self, cam, initialization, images, slot)
 FusedMappingLoop._map_view = spy

@@ -27,7 +27,6 @@ leaves its gradients in the sinks, its isotropy term and exposure gradients are 
 the first optimiser step that follows (tests/test_gpu_fused.py replays the reference fixture through it).
 """
 import collections
-import os
 import ctypes as C
 
 import numpy as np
@@ -41,10 +40,57 @@ _GROUPS = ["xyz", "f_dc", "opacity", "scaling", "rotation"]     # order expected
 
 
 class _Plan:
-    pass
+    """Launch structs of one parameter set (FusedMappingLoop._plan)."""
 
 
-class _ViewBuffers:
+class _CachedView:
+    """A camera's cached SgrMapView (FusedMappingLoop._map_view): valid for `key`; `n` and `gen` are the map size and the
+    buffer generation its per-Gaussian and workspace pointers were filled in for."""
+
+    def __init__(self, key, view, n, gen):
+        self.key, self.view, self.n, self.gen = key, view, n, gen
+
+
+class _SpanArrays:
+    """The (window, pool) SgrMapView arrays of the spans of one map() call (FusedMappingLoop._span_arrays).  `window_gens`: the
+    window cameras' buffer generations; `protect`: the workspaces the arrays point into (_ws_protect while they are in use)."""
+
+    def __init__(self, ident, gen, window_gens, win, pool, protect):
+        self.ident, self.gen, self.window_gens, self.win, self.pool, self.protect = ident, gen, window_gens, win, pool, protect
+
+
+class _PreparedSpan:
+    """Everything sgr_map_run needs for one span (FusedMappingLoop._prepare_span); `keep`: the ctypes arrays `run` points into."""
+
+    def __init__(self, run, pl, n_it, per, window_cams, pool_cams, picks, keep):
+        self.run, self.pl, self.n_it, self.per = run, pl, n_it, per
+        self.window_cams, self.pool_cams, self.picks, self.keep = window_cams, pool_cams, picks, keep
+
+
+class _Transaction:
+    """The open transaction (FusedMappingLoop._txn_begin): the mutated tensors, their snapshot, the journal of enqueue closures
+    and the Python-side state as of the snapshot."""
+
+    def __init__(self, tensors, saved, flat_live, py):
+        self.tensors, self.saved, self.flat_live, self.py = tensors, saved, flat_live, py
+        self.journal = []
+
+
+class _WorkspaceOwner:
+    """Holder of a (saved, scratch) workspace: a camera's buffers (_ViewBuffers) or a shared slot (_Slot)."""
+    is_slot = False
+
+    def __init__(self):
+        self.gen = 0               # bumped whenever a buffer a cached SgrMapView points into is re-allocated (ints, saved, scratch)
+        self.saved = self.scratch = None
+        self.clean = False         # the saved block went through a forward (its per-tile counters are zero)
+        self.ran = False           # a forward has run on the saved block (at THIS map size: _ViewBuffers.new_map)
+        self.ovf_seen = 0          # SavedHeader.overflow_events as of the last check (sticky on the device, see _apply_headers)
+        self.capacity = 0
+        self.mv = None             # (images, slot) -> _CachedView
+
+
+class _ViewBuffers(_WorkspaceOwner):
     """Per-camera device buffers.  They SURVIVE changes of the map size (every keyframe appends Gaussians, every densification
     changes N): re-making ~150 cameras' buffers -- and above all their ~250 MB workspaces, whose sizes never repeat exactly, so
     the caching allocator went to hipMalloc for them -- cost a converged session 25-30 ms of host time per keyframe, during which
@@ -52,6 +98,7 @@ class _ViewBuffers:
     and re-carved."""
 
     def __init__(self, H, W, N, dev):
+        super().__init__()
         f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
         self.dev = dev
         self.color, self.depth, self.opacity = f(3, H, W), f(1, H, W), f(1, H, W)
@@ -62,15 +109,8 @@ class _ViewBuffers:
         ntiles = ((H + 7) // 8) * ((W + 7) // 8)
         self.loss_scratch = torch.empty(max(1024, ntiles) * 16, dtype=torch.uint8, device=dev)   # one LossPart per 8x8 tile
         self._ibuf, self._icap = None, 0
-        self.gen = 0               # bumped whenever a buffer a cached SgrMapView points into is re-allocated (ints, saved, scratch)
-        self.saved = None
-        self.scratch = None
-        self.clean = False         # the saved block went through a forward (its per-tile counters are zero)
-        self.ovf_seen = 0          # SavedHeader.overflow_events as of the last check (sticky on the device, see _apply_headers)
-        self.capacity = 0
         self.gt_depth = None
         self.depth_src = None
-        self.mv = None
         self.new_map(N)
 
     def new_map(self, N):
@@ -131,17 +171,9 @@ def _index(rows, device):
     return _INDEX_STAGE.get(list(rows), device)
 
 
-class _Slot:
+class _Slot(_WorkspaceOwner):
     """A workspace that belongs to no camera: pick j of every iteration of a span renders in slot j."""
     is_slot = True
-
-    def __init__(self):
-        self.saved = self.scratch = None
-        self.clean = self.ran = False
-        self.ovf_seen = 0
-        self.capacity = 0
-        self.mv = None
-        self.gen = 0
 
 
 class _ExposureSlab:
@@ -273,21 +305,13 @@ class FusedMappingLoop(MappingLoop):
         # snapshot, grows the capacity and re-issues the journal (_txn_commit), so a view that overflowed takes part in every step
         # after all, like upstream's rasterizer, which sizes its buffers inside the call (README.md:88-92 module).
         self._txn = None
-        # True: a span whose views run on carried-over pair-count ESTIMATES sends its first iteration ahead and reads its headers back
-        # before the rest is enqueued (round 3: an estimate that was short then cost one iteration, not a span of dropped views).
-        # With transactions nothing is ever dropped -- a short estimate costs a replay of the span, once in tens of keyframes -- and the
-        # extra synchronisation per keyframe (GPU idle ~1 ms behind it, scripts/session_timeline.py) is the more expensive of the two.
-        self.verify_estimates = os.environ.get("SPLAT_VERIFY_ESTIMATES", "0") == "1"
-        self._span_cache = None    # (window, pool) SgrMapView arrays of the spans of one map() call (_span_arrays)
-        self.cache_span_arrays = os.environ.get("SPLAT_SPAN_CACHE", "1") != "0"      # (0: A/B measurements of the host path)
-        self.keep_structs_over_keyframes = os.environ.get("SPLAT_KEYFRAME_STRUCTS", "1") != "0"   # (0: round-5 behaviour, for A/B)
-        self.snapshot_store = os.environ.get("SPLAT_SNAPSHOT_STORE", "1") != "0"                  # (0: a fresh buffer per tensor and map size, for A/B)
+        self._span_cache = None    # _SpanArrays of the spans of one map() call (_span_arrays, _drop_span_arrays)
         self._txn_pool = None      # snapshot buffers, reused while the tensor shapes stay
         self._txn_store = None     # ... the byte store they are views of (kept with head-room across map sizes)
         self._replaying = False
         self.replayed_transactions = 0
         self._hdr_pinned = None
-        self._gen = 0              # bumped whenever cached launch structs go stale (capacity, hints, buffers)
+        self._gen = 0              # bumped whenever every cached launch struct goes stale (_views_dirty: capacity)
         self._pair_hint = {}       # camera uid -> (measured pair count, map size it was measured at)
         self._list_hint = {}       # camera uid -> longest per-tile list measured (header word 10): picks the tile kernels' sort build
         self._ws_bytes = {}        # (N, H, W, capacity) -> (saved bytes, scratch bytes)
@@ -325,7 +349,7 @@ class FusedMappingLoop(MappingLoop):
         self._ws_owners.clear()
         self._slots = []
         self._txn = None
-        self._span_cache = None
+        self._drop_span_arrays()
 
     # ------------------------------------------------------------------------------------------------ state
     def set_parallel(self, world, rank, split_views=True, sync="zero1", comm=None):
@@ -553,7 +577,7 @@ class FusedMappingLoop(MappingLoop):
         recently used owner that the call being built does not need, else new blocks (with head-room)."""
         me = id(vb)
         self._ws_owners.pop(me, None)
-        if not getattr(vb, "is_slot", False) and len(self._ws_owners) >= self.max_live_ws:
+        if not vb.is_slot and len(self._ws_owners) >= self.max_live_ws:
             for k, old in self._ws_owners.items():
                 if k not in self._ws_protect:
                     del self._ws_owners[k]
@@ -565,10 +589,8 @@ class FusedMappingLoop(MappingLoop):
                     old.clean = old.ran = False
                     old.ovf_seen = 0
                     old.mv = None
-                    # whoever cached structs that point into the evicted blocks must not use them again (the span cache
-                    # holds COPIES of the window cameras' structs and is only validated by these generations)
-                    old.gen += 1
-                    self._span_cache = None
+                    old.gen += 1      # (whoever cached structs that point into the evicted blocks must not use them again)
+                    self._drop_span_arrays()
                     break
         if vb.saved is None or vb.saved.numel() < sb:
             vb.saved = torch.empty((int(sb * 1.3) + (1 << 20)) // 256 * 256, dtype=torch.uint8, device=self.device)
@@ -578,7 +600,7 @@ class FusedMappingLoop(MappingLoop):
         if vb.scratch is None or vb.scratch.numel() < tb:
             vb.scratch = torch.empty((int(tb * 1.3) + (1 << 20)) // 256 * 256, dtype=torch.uint8, device=self.device)
             vb.gen += 1
-        if not getattr(vb, "is_slot", False):
+        if not vb.is_slot:
             self._ws_owners[me] = vb
 
     def _max_list(self):
@@ -601,7 +623,7 @@ class FusedMappingLoop(MappingLoop):
     def _apply_header(self, uid, vb, w):
         R, ov, longest = int(w[0]), int(w[1]), int(w[10])
         vb.pairs, vb.estimated = R, False
-        if not getattr(vb, "is_slot", False):         # (a slot's count belongs to whichever camera rendered in it last)
+        if not vb.is_slot:                            # (a slot's count belongs to whichever camera rendered in it last)
             self._pair_hint[uid] = (R, self.gaussians._xyz.shape[0])
         if longest != self._list_hint.get(uid):
             old = self._build_class()
@@ -672,7 +694,7 @@ class FusedMappingLoop(MappingLoop):
             if not vb.clean:
                 vb.clean = True
                 for ent in (vb.mv or {}).values():
-                    ent[1].ws.counters_clean = 1
+                    ent.view.ws.counters_clean = 1
 
     # ------------------------------------------------------------------------------------------------ pieces
     def _inputs(self):
@@ -703,9 +725,9 @@ class FusedMappingLoop(MappingLoop):
         hit = vb.mv.get((images, slot))
         gm = self.gaussians
         N, H, W = gm._xyz.shape[0], int(cam.image_height), int(cam.image_width)
-        if hit is not None and hit[0] == key:
-            mv = hit[1]
-            if hit[2] != N or hit[3] != vb.gen:
+        if hit is not None and hit.key == key:
+            mv = hit.view
+            if hit.n != N or hit.gen != vb.gen:
                 # the map changed size, or one of the camera's buffers was re-allocated meanwhile (an entry that is only compared by
                 # N would point at freed radii / workspace memory once N returns to an earlier value): same camera -- only what
                 # depends on N or on the buffers is re-filled
@@ -713,10 +735,10 @@ class FusedMappingLoop(MappingLoop):
                 mv.out.radii, mv.out.n_touched = vb.radii.data_ptr(), vb.n_touched.data_ptr()
                 if not slot:
                     mv.ws = self._workspace(vb, N, H, W, self._cap)
-                hit[2], hit[3] = N, vb.gen
+                hit.n, hit.gen = N, vb.gen
             elif not slot and (vb.saved is None or id(vb) not in self._ws_owners):
                 mv.ws = self._workspace(vb, N, H, W, self._cap)         # (its blocks went to another camera meanwhile)
-                hit[3] = vb.gen
+                hit.gen = vb.gen
             elif not slot:
                 self._ws_owners.move_to_end(id(vb))
             return mv
@@ -733,7 +755,7 @@ class FusedMappingLoop(MappingLoop):
         mv.dL_dexposure = vb.d_exp.data_ptr() if row is None else self._exp.grad.data_ptr() + 8 * row
         mv.dL_dtau = vb.d_tau.data_ptr() if self.keyframe_optimizers is not None else None
         mv.loss_scratch, mv.loss_scratch_bytes = vb.loss_scratch.data_ptr(), vb.loss_scratch.numel()
-        vb.mv[(images, slot)] = [key, mv, N, vb.gen]
+        vb.mv[(images, slot)] = _CachedView(key, mv, N, vb.gen)
         return mv
 
     def _settle_capacity(self, cams):
@@ -761,30 +783,42 @@ class FusedMappingLoop(MappingLoop):
 
     def _span_arrays(self, window_cams, pool_cams, initialization):
         """(window array, pool array) of a span -- SgrMapView structs for sgr_map_run -- built ONCE for the spans that share them: a
-        keyframe's map() call goes out as 2 + 6 + 52 iterations (plus a verified first iteration), all with the same window and the
-        same pool (every other keyframe: hundreds late in a session).  Re-making both arrays and re-settling the capacity per span
-        cost a 20-keyframe session 7 ms of host time per keyframe, most of it with the GPU idle behind the keyframe-selection
-        read-back (scripts/session_timeline.py).  Valid while nothing they point into has changed: map size, capacity / hints
-        generation, the cameras' own versions and buffers."""
+        keyframe's map() call goes out as 2 + 6 + 52 iterations, all with the same window and the same pool (every other keyframe:
+        hundreds late in a session).  Re-making both arrays and re-settling the capacity per span cost a 20-keyframe session 7 ms
+        of host time per keyframe, most of it with the GPU idle behind the keyframe-selection read-back
+        (scripts/session_timeline.py).  Valid while nothing they point into has changed: map size, capacity generation, the
+        cameras' own versions and buffers -- and whatever _drop_span_arrays lists."""
         N = self.gaussians._xyz.shape[0]
         cams = list(window_cams) + list(pool_cams)
         ident = (N, bool(initialization), len(window_cams), tuple(id(c) for c in cams), tuple(c._version for c in cams))
-        hit = self._span_cache if self.cache_span_arrays else None
-        if hit is not None and hit[0] == ident and hit[1] == self._gen and all(self._views[c.uid].gen == g for c, g in zip(window_cams, hit[2])):
-            self._ws_protect = hit[5]
+        sa = self._span_cache
+        if (sa is not None and sa.ident == ident and sa.gen == self._gen
+                and all(self._views[c.uid].gen == g for c, g in zip(window_cams, sa.window_gens))):
+            self._ws_protect = sa.protect
             for i, c in enumerate(window_cams):          # (the array holds COPIES of the cached structs: a block that has been through a
                 vb = self._views[c.uid]                  #  forward since needs no zeroing launch in front of the next span)
                 if vb.clean:
-                    hit[3][i].ws.counters_clean = 1
+                    sa.win[i].ws.counters_clean = 1
                 if id(vb) in self._ws_owners:            # a hit never goes through _workspace(): keep the window's blocks the most
                     self._ws_owners.move_to_end(id(vb))  # recently used ones, or they become the likeliest eviction victims
-            return hit[3], hit[4]
+            return sa.win, sa.pool
         self._settle_capacity(cams)                                              # estimates for new cameras, ONE capacity
         win = self._views_array(window_cams, initialization, images=False, settle=False) if window_cams else None
         protect = self._ws_protect
         pool = self._views_array(pool_cams, initialization, images=False, slot=True, settle=False) if pool_cams else None
-        self._span_cache = (ident, self._gen, [self._views[c.uid].gen for c in window_cams], win, pool, protect)
+        self._span_cache = _SpanArrays(ident, self._gen, [self._views[c.uid].gen for c in window_cams], win, pool, protect)
         return win, pool
+
+    def _drop_span_arrays(self):
+        """Forgets the span arrays.  They hold COPIES of the window cameras' structs, so everything that changes a struct without
+        bumping _gen or a window camera's buffer generation drops them:
+          reset                      a new mapping problem (cameras, buffers and hints all start over);
+          _acquire_blocks            a camera's blocks were evicted (LRU): the copies still point into them;
+          _hint_changed              the structs were patched in place (max_list_hint): the copies carry the old hint;
+          build_keyframe_optimizers  the cameras' exposure parameters may have been re-bound to the slab (other addresses);
+          map()                      between two calls renders of other frames may have re-assigned workspaces (re-making the
+                                     arrays once per call is 0.14 ms)."""
+        self._span_cache = None
 
     def _slot_workspaces(self, count, N, H, W):
         """`count` shared workspace slots at the current capacity (SgrMapRun.pick_ws)."""
@@ -868,45 +902,19 @@ class FusedMappingLoop(MappingLoop):
                 st.exp_lr, st.exp_beta1, st.exp_beta2, st.exp_eps = 0.01, 0.9, 0.999, 1e-8
         return st
 
-    def _run_span(self, window_cams, pool_cams, picks, lrs, iso_weight, exposure, stats=True, initialization=False, verified=False):
+    def _run_span(self, window_cams, pool_cams, picks, lrs, iso_weight, exposure, stats=True, initialization=False):
         """len(lrs) regular iterations with ONE host call (sgr_map_run): iteration k renders window_cams plus
-        pool_cams[picks[k]] and steps Adam with the xyz learning rate lrs[k].
-        A view whose workspace is sized by a carried-over ESTIMATE of its pair count (buffers are new after the map changed
-        size) could be truncated for the whole span without anybody looking: the first iteration then runs on its own and
-        the headers of its views are read back before the rest of the span is enqueued (one synchronisation per span that
-        follows a change of the map; views that only appear later in the span are covered by the periodic check, which warns)."""
-        n_it = len(lrs)
-        if self._parallel() or n_it == 0:
+        pool_cams[picks[k]] and steps Adam with the xyz learning rate lrs[k].  Part of the open transaction: a view whose
+        carried-over pair-count estimate falls short is found by the check that closes it, and the span is issued again (a
+        replay prepares its own launch structs at the corrected capacity)."""
+        if self._parallel() or not lrs:
             raise RuntimeError("_run_span is the single-GPU fast path")
         self._span_arrays(window_cams, pool_cams, initialization)                # estimates for new cameras, ONE capacity (cached per map size)
-        per0 = len(picks) // n_it if picks else 0
-        if (n_it > 1 and not verified and not self._replaying and self.verify_estimates
-                and any(self._views[c.uid].estimated for c in list(window_cams) + [pool_cams[k] for k in picks[:per0]])):
-            self._run_span(window_cams, pool_cams, picks[:per0], lrs[:1], iso_weight, exposure, stats, initialization, verified=True)
-            # the launch structs of the rest are built while that iteration runs; the read-back then only decides whether they stand
-            rest = (window_cams, pool_cams, picks[per0:], lrs[1:], iso_weight, exposure, stats, initialization)
-            prep = self._prepare_span(*rest)
-            if not self._txn_commit():               # (an estimate that was short: the iteration has been re-run at the right capacity)
-                for k in picks[:per0]:               # (rendered in the slots that were just read back: their estimates held)
-                    self._views[pool_cams[k].uid].estimated = False
-            return self._span_entry(rest, prep)
-        return self._span_entry((window_cams, pool_cams, picks, lrs, iso_weight, exposure, stats, initialization))
-
-    def _span_entry(self, args, prep=None):
-        """Enqueues a span as part of the open transaction.  `prep`: launch structs built ahead of time -- used if the capacity /
-        sort build they were made for still stands (a replay after a correction builds its own)."""
-        args = tuple(list(a) if isinstance(a, (list, tuple)) else a for a in args)
-        box = [prep]
-
-        def fn():
-            pr, box[0] = box[0], None
-            if pr is None or pr[-1] != self._gen:
-                pr = self._prepare_span(*args)
-            self._launch_span(pr)
-        return self._txn_do(fn)
+        args = (list(window_cams), list(pool_cams), list(picks), list(lrs), iso_weight, exposure, stats, initialization)
+        return self._txn_do(lambda: self._launch_span(self._prepare_span(*args)))
 
     def _prepare_span(self, window_cams, pool_cams, picks, lrs, iso_weight, exposure, stats, initialization):
-        """Everything sgr_map_run needs, as ctypes objects (kept alive by the returned tuple)."""
+        """Everything sgr_map_run needs, as ctypes objects (kept alive by the returned _PreparedSpan)."""
         n_it = len(lrs)
         pl = self._plan()
         win, pool = self._span_arrays(window_cams, pool_cams, initialization)    # (ONE capacity for the window and the pool)
@@ -934,22 +942,22 @@ class FusedMappingLoop(MappingLoop):
                 (self._exp.row_of(c) if self._exp is not None and self._exp.row_of(c) in self._exp_rows else -1)
                 for c in pool_cams])
             run.pool_exp_row = rows
-        return run, pl, n_it, per, list(window_cams), list(pool_cams), list(picks), (win, pool, pk, lr, slots, rows), self._gen
+        return _PreparedSpan(run, pl, n_it, per, list(window_cams), list(pool_cams), list(picks), (win, pool, pk, lr, slots, rows))
 
-    def _launch_span(self, prep):
-        run, pl, n_it, per, window_cams, pool_cams, picks, _keep, _gen = prep
+    def _launch_span(self, sp):
         self._clean_flat()
-        rc = self.lib.sgr_map_run(C.byref(run), self._stream())
+        rc = self.lib.sgr_map_run(C.byref(sp.run), self._stream())
         nat.check(rc, "sgr_map_run")
         self.gaussians.invalidate_activations()    # parameters changed through raw pointers: cached torch activations are stale
         self._acc_clean = True
-        self._mark_clean(window_cams)
+        self._mark_clean(sp.window_cams)
+        per, picks = sp.per, sp.picks
         for sl in self._slots[:per]:
             sl.clean = sl.ran = True
-        self._last_pick_slots = {pool_cams[k].uid: j for j, k in enumerate(picks[len(picks) - per:])} if per else {}
-        for g, stt in pl.states:                 # the library advanced pl.groups[k].step; mirror it in torch's state
-            stt["step"] += n_it
-        pl.frest_state["step"] += n_it
+        self._last_pick_slots = {sp.pool_cams[k].uid: j for j, k in enumerate(picks[len(picks) - per:])} if per else {}
+        for g, stt in sp.pl.states:              # the library advanced pl.groups[k].step; mirror it in torch's state
+            stt["step"] += sp.n_it
+        sp.pl.frest_state["step"] += sp.n_it
 
     def _run_span_ranks(self, window_cams, pool_cams, picks, lrs, iso_weight, exposure, stats=True):
         args = (list(window_cams), list(pool_cams), list(picks), list(lrs), iso_weight, exposure, stats)
@@ -964,9 +972,7 @@ class FusedMappingLoop(MappingLoop):
         n_it = len(lrs)
         pl = self._plan()
         nw, per = len(window_cams), (len(picks) // n_it if picks else 0)
-        mine_w = self._local(list(window_cams) + [None] * per)               # positions of an iteration this rank renders
-        pos = list(range(nw + per))[self.rank::self.world] if self.split_views else list(range(nw + per))
-        del mine_w
+        pos = list(range(nw + per))[self.rank::self.world] if self.split_views else list(range(nw + per))   # positions this rank renders
         cams_needed = [c for i, c in enumerate(window_cams) if i in pos] + (list(pool_cams) if any(i >= nw for i in pos) else [])
         if cams_needed:
             self._settle_capacity(cams_needed)                             # estimates for new cameras, ONE capacity
@@ -1137,9 +1143,7 @@ class FusedMappingLoop(MappingLoop):
         # (no _views_dirty() here any more: what a cached launch struct takes from the exposure slab -- the addresses of the camera's
         #  a / b and of its gradient row -- is part of the struct's key (_map_view).  Dropping every camera's structs at EVERY keyframe
         #  cost a late session ~190 rebuilds = 3-5 ms per keyframe with the GPU idle, growing with the number of keyframes.)
-        self._span_cache = None
-        if not self.keep_structs_over_keyframes:
-            self._views_dirty()
+        self._drop_span_arrays()
         pose_opt = bool(self.config["mapping"]["BA"]) and not self.config["mapping"]["Training"].get("gt_camera", False)
         self.keyframe_optimizers = None
         if pose_opt:                                   # pose deltas (off by default) stay on torch.optim.Adam
@@ -1162,8 +1166,8 @@ class FusedMappingLoop(MappingLoop):
         hint = self._max_list()
         for vb in self._views.values():
             for ent in (vb.mv or {}).values():
-                ent[1].ws.max_list_hint = hint
-        self._span_cache = None            # (its arrays hold COPIES of the structs)
+                ent.view.ws.max_list_hint = hint
+        self._drop_span_arrays()
 
     def _views_dirty(self):
         self._gen += 1
@@ -1309,8 +1313,6 @@ class FusedMappingLoop(MappingLoop):
         (new Gaussians, prune passes), and eighteen torch.empty_like of never-seen sizes were eighteen allocator misses -- 1.5 ms per
         snapshot, two or three snapshots per keyframe with the GPU idle behind them (scripts/micro/txn_begin_parts.py: 4 ms per
         keyframe of a young session)."""
-        if not self.snapshot_store:
-            return [torch.empty_like(t) for t in ts]
         offs, need = [], 0
         for t in ts:
             offs.append(need)
@@ -1337,15 +1339,13 @@ class FusedMappingLoop(MappingLoop):
         with torch.no_grad():
             for dt in {t.dtype for t in ts}:
                 torch._foreach_copy_([b for b, t in zip(pool, ts) if t.dtype == dt], [t for t in ts if t.dtype == dt])
-        txn = _Plan()
-        txn.tensors, txn.saved, txn.flat_live, txn.journal = ts, pool, flat_live, []
         steps = [gm.optimizer.state[g["params"][0]]["step"] for g in gm.optimizer.param_groups
                  if gm.optimizer.state.get(g["params"][0])]
-        txn.py = {"steps": [(t, float(t)) for t in steps],
-                  "stale_iso": self._stale_iso, "acc_clean": self._acc_clean, "flat_dirty": self._flat_dirty,
-                  "exp_stale_rows": set(self._exp.stale_rows) if self._exp is not None else None,
-                  "stale_moments": self._zero.get("stale_moments") if self._zero is not None else None}
-        self._txn = txn
+        py = {"steps": [(t, float(t)) for t in steps],
+              "stale_iso": self._stale_iso, "acc_clean": self._acc_clean, "flat_dirty": self._flat_dirty,
+              "exp_stale_rows": set(self._exp.stale_rows) if self._exp is not None else None,
+              "stale_moments": self._zero.get("stale_moments") if self._zero is not None else None}
+        self._txn = _Transaction(ts, pool, flat_live, py)
 
     def _txn_do(self, fn):
         """Runs a state-changing piece of enqueue work as part of the open transaction (opens one if needed)."""
@@ -1416,9 +1416,6 @@ class FusedMappingLoop(MappingLoop):
         """Did any camera's forward exceed the pair capacity since the last check?  One synchronisation; the answer covers
         everything enqueued so far, and whatever was affected has been re-run (see _txn_commit) when this returns."""
         return self._txn_commit()
-
-    def _periodic_check(self, steady=False):
-        self._txn_commit()
 
     def _tick(self):
         self._since_check += 1
@@ -1508,8 +1505,7 @@ class FusedMappingLoop(MappingLoop):
         random_viewpoint_stack = [v for idx, v in self.viewpoints.items() if idx not in cw]
         pose_opt = self.keyframe_optimizers is not None
         gaussian_split = False
-        self._span_cache = None      # the span arrays are shared by the spans of ONE map() call (between calls renders of other frames may
-                                     # have re-assigned workspaces; re-making them once per call is 0.14 ms)
+        self._drop_span_arrays()     # (the span arrays are shared by the spans of ONE call)
         it = -1
         while it + 1 < iters:
             it += 1

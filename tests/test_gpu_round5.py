@@ -179,7 +179,6 @@ def _drive(kind, sabotage, estimated=False, fresh_plan=False):
     from splat_slam_amd.fused import FusedMappingLoop
     syn, params, cams = _dense_scene()
     f = _loop(FusedMappingLoop, syn, params, cams, [0, 1, 2])
-    f.verify_estimates = bool(estimated)       # (the first iteration of a span on estimated counts goes ahead and is checked on its own)
     f.iteration_count = 50
     torch.manual_seed(3)
     np.random.seed(3)

@@ -210,7 +210,6 @@ def test_a_forward_that_overflows_in_the_middle_of_a_span_is_replayed():
             f._cap = (others + pairs[big.uid]) // 2
             f.capacity_floor = min(f.capacity_floor, f._cap)
             f._views_dirty()
-        f.verify_estimates = False
         # the span's picks are torch.randperm draws (mapper.py:470): a seed whose 12 iterations pick the greedy camera in the MIDDLE only
         pool = [c for c in cams if c.uid not in f.current_window]
         for seed in range(500):
