@@ -14,6 +14,12 @@
  *   sgr_saved_bytes,
  *   sgr_scratch_bytes      -> the resizeFunctional geom/binning/image buffer callbacks of the same module.
  *   sgr_mapping_loss       -> get_loss_mapping / get_loss_mapping_rgbd, thirdparty/monogs/utils/slam_utils.py:71-105
+ *   sgr_ssim_scratch_bytes,
+ *   sgr_ssim,
+ *   sgr_ssim_backward      -> ssim of thirdparty/gaussian_splatting/utils/loss_utils.py:61-101 (the ssim_loss: True mapping loss,
+ *                             thirdparty/monogs/utils/slam_utils.py:89-98, imported at src/mapper.py:35) and its autograd backward
+ *   sgr_render_metrics     -> the PSNR / SSIM / depth-L1 part of eval_rendering, src/utils/eval_utils.py:90-128, called from
+ *                             src/slam.py:153,193
  *   sgr_adam_step          -> torch.optim.Adam(eps=1e-15) over the GaussianModel groups,
  *                             thirdparty/gaussian_splatting/scene/gaussian_model.py:264-313, stepped at
  *                             src/mapper.py:352,557,703
@@ -266,6 +272,39 @@ int sgr_mapping_loss(int32_t H, int32_t W, const float* image, const float* dept
                      float alpha, float rgb_boundary_threshold, float upstream,
                      float* loss, float* dL_dimage, float* dL_ddepth, float* dL_dexp_a, float* dL_dexp_b,
                      void* scratch, size_t scratch_bytes, void* stream);
+
+/* SSIM (loss_utils.py:36-101): 11-tap Gaussian window of sigma 1.5 (the 2-D window its outer product), every channel filtered on
+ * its own with zero padding 5, C1 = 0.01^2, C2 = 0.03^2.  img1, img2: [B,C,H,W].  sgr_ssim writes the mean of the SSIM map of each
+ * image to ssim_out[B] (the reference's size_average=True result is their mean).  With `maps` != NULL ([3,B,C,H,W]) it also writes
+ * the three per-pixel derivatives of an image's mean, divided by C*H*W, that sgr_ssim_backward needs:
+ *   dm = d/dmu1 (through the sigmas), d11 = d/dE[x^2], d12 = d/dE[xy]   (x = img1, y = img2, E = the window average).
+ * sgr_ssim_backward: dL/dimg1 = u_b * (G*dm + 2 x (G*d11) + y (G*d12)) with u_b = upstream[b * upstream_stride] * upstream_scale
+ * (device scalar: no host sync; stride 0 broadcasts one value).  Only img1 is differentiated (ssim(image, gt_image)).
+ * `scratch` (sgr_ssim_scratch_bytes) holds the per-workgroup partials: fixed-order sums, bitwise reproducible. */
+size_t sgr_ssim_scratch_bytes(int32_t B, int32_t C, int32_t H, int32_t W);
+int sgr_ssim(int32_t B, int32_t C, int32_t H, int32_t W, const float* img1, const float* img2, float* ssim_out, float* maps,
+             void* scratch, size_t scratch_bytes, void* stream);
+int sgr_ssim_backward(int32_t B, int32_t C, int32_t H, int32_t W, const float* img1, const float* img2, const float* maps,
+                      const float* upstream, int32_t upstream_stride, float upstream_scale, float* dL_dimg1, void* stream);
+
+/* Rendering metrics of eval_rendering (eval_utils.py:90-128) for n frames of [C,H,W] in one call (launches of up to 16 frames
+ * each plus one final pass), host array `frames`:
+ *   image    = clamp(exp(a) * render + b, 0, 1)  (:96-100; exposure NULL = identity, the first frame),
+ *   psnr     = 20 log10(1 / sqrt(mean over gt > 0 of (image - gt)^2))   (:109,123, image_utils.py:19-21),
+ *   ssim     = ssim(image, gt_image)                                      (:124),
+ *   depth_l1 = mean over depth > 0 and gt_depth > 0 of |global_scale * depth - gt_depth|   (:116-120; depth [H,W] may be NULL).
+ * out[3 * f + 0..2] = (psnr, ssim, depth_l1) of frame f on the device.  An empty mask gives NaN (the reference's 0/0), a perfect
+ * frame PSNR inf.  scratch: sgr_ssim_scratch_bytes(n, C, H, W). */
+typedef struct SgrMetricFrame {
+  const float* render;         /* [C,H,W] */
+  const float* gt_image;       /* [C,H,W] */
+  const float* depth;          /* [H,W] rendered depth, or NULL */
+  const float* gt_depth;       /* [H,W], or NULL */
+  const float* exposure_a;     /* device scalar, or NULL */
+  const float* exposure_b;     /* device scalar, or NULL */
+} SgrMetricFrame;
+int sgr_render_metrics(int32_t n, const SgrMetricFrame* frames, int32_t C, int32_t H, int32_t W, float global_scale, float* out,
+                       void* scratch, size_t scratch_bytes, void* stream);
 
 /* One torch.optim.Adam step (no weight decay, no amsgrad) on a flat parameter slab. step = the value AFTER
  * increment (1 on the first call).  lr may differ per call (update_learning_rate, gaussian_model.py:315-329). */

@@ -94,6 +94,10 @@ class SgrDeformFrame(C.Structure):
                 ("height", C.c_int32), ("width", C.c_int32), ("depth_new", _fp), ("depth_old", _fp)]
 
 
+class SgrMetricFrame(C.Structure):
+    _fields_ = [("render", _fp), ("gt_image", _fp), ("depth", _fp), ("gt_depth", _fp), ("exposure_a", _fp), ("exposure_b", _fp)]
+
+
 class SgrRowTensor(C.Structure):
     _fields_ = [("in_", _fp), ("out", _fp), ("row_bytes", C.c_int32)]
 
@@ -122,6 +126,11 @@ SIGNATURES = {
     "sgr_profile_read": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int64)]),
     "sgr_mapping_loss": (C.c_int, [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, C.c_float, C.c_float,
                                    C.c_float, _fp, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "sgr_ssim_scratch_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "sgr_ssim": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "sgr_ssim_backward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_int32, C.c_float, _fp, _fp]),
+    "sgr_render_metrics": (C.c_int, [C.c_int32, C.POINTER(SgrMetricFrame), C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp, _fp,
+                                     C.c_size_t, _fp]),
     "sgr_adam_step": (C.c_int, [C.c_int64, _fp, _fp, _fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float,
                                 C.c_int64, _fp]),
     "sgr_adam_step_multi": (C.c_int, [C.c_int32, C.POINTER(SgrAdamTensor), C.c_float, C.c_float, C.c_float, C.c_float, _fp]),

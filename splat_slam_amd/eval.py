@@ -1,9 +1,13 @@
-"""Rendering metric of the hot path -- PSNR as computed by eval_rendering,
-/root/reference/src/utils/eval_utils.py:90-123 with psnr() of
-/root/reference/thirdparty/gaussian_splatting/utils/image_utils.py:19-21.  (SSIM / LPIPS / mesh metrics need
-third-party evaluation libraries and are out of scope)"""
+"""Rendering metrics of eval_rendering, /root/reference/src/utils/eval_utils.py:64-197: PSNR (psnr() of
+/root/reference/thirdparty/gaussian_splatting/utils/image_utils.py:19-21), SSIM (the reference's own in-tree
+loss_utils.ssim, thirdparty/gaussian_splatting/utils/loss_utils.py:61-101) and the rendered depth's L1 error.
+`eval_rendering` computes all three on the HIP kernels (sgr_render_metrics); `eval_rendering_psnr` is the PSNR-only
+torch formulation.  LPIPS is not computed: it needs pretrained AlexNet weights from outside the project.  The mesh
+metrics (TSDF fusion, open3d) are out of scope as well."""
+import numpy as np
 import torch
 
+from splat_slam_amd import _native as nat
 from splat_slam_amd.renderer import render
 
 
@@ -25,3 +29,57 @@ def eval_rendering_psnr(frames, gaussians, pipe, background):
         mask = gt > 0
         scores.append(psnr(image[mask].unsqueeze(0), gt[mask].unsqueeze(0)).item())
     return scores
+
+
+_METRIC_CHUNK = 16          # frames rendered, then measured in one launch (renders of a chunk stay alive until it is measured)
+
+
+def _device_depth(d, device):
+    if not torch.is_tensor(d):
+        d = torch.from_numpy(d)
+    return d.to(dtype=torch.float32, device=device).reshape(d.shape[-2:]).contiguous()
+
+
+@torch.no_grad()
+def eval_rendering(frames, gaussians, pipe, background, gt_depths=None, global_scale=1.0):
+    """eval_rendering's per-frame metrics (eval_utils.py:90-128, means as :190-194) on the HIP kernels: frames is a list of Camera
+    in keyframe order; every frame but the first gets its exposure compensation (:96-99), the image is clamped to [0, 1];
+    PSNR over the elements where the ground truth is > 0 (:109,123), SSIM of the whole image (:124), depth L1 of
+    global_scale * rendered depth over pixels where both depths are > 0 (:116-120).  gt_depths: one [H,W] per frame (default:
+    each frame's `depth`).  One copy to the host per call.  A frame without a valid depth pixel gives NaN (the reference's 0/0), a
+    perfect frame PSNR inf.  LPIPS is not computed (module docstring)."""
+    if not frames:
+        raise ValueError("eval_rendering: no frames")
+    if gt_depths is not None and len(gt_depths) != len(frames):
+        raise ValueError(f"eval_rendering: {len(gt_depths)} ground-truth depths for {len(frames)} frames")
+    lib = nat.lib()
+    dev = frames[0].original_image.device
+    if dev.type != "cuda":
+        raise RuntimeError("eval_rendering needs GPU tensors (HIP only, no CPU fallback)")
+    C, H, W = frames[0].original_image.shape
+    n = len(frames)
+    scratch_bytes = lib.sgr_ssim_scratch_bytes(_METRIC_CHUNK, C, H, W)
+    arena = torch.empty(3 * n + scratch_bytes // 4, dtype=torch.float32, device=dev)
+    out, scratch = arena[:3 * n], arena[3 * n:]
+    stream = torch.cuda.current_stream().cuda_stream
+    for c0 in range(0, n, _METRIC_CHUNK):
+        keep, table = [], (nat.SgrMetricFrame * min(_METRIC_CHUNK, n - c0))()
+        for i, k in enumerate(range(c0, c0 + len(table))):
+            frame = frames[k]
+            pkg = render(frame, gaussians, pipe, background)
+            r, d = pkg["render"].contiguous(), pkg["depth"].contiguous()
+            gt = frame.original_image.contiguous()
+            gd = _device_depth(frame.depth if gt_depths is None else gt_depths[k], dev)
+            if tuple(gt.shape) != (C, H, W) or tuple(r.shape) != (C, H, W) or gt.dtype != torch.float32:
+                raise ValueError(f"eval_rendering: frame {k} is {tuple(gt.shape)} {gt.dtype}, not fp32 {(C, H, W)}")
+            a, b = (frame.exposure_a, frame.exposure_b) if k > 0 else (None, None)
+            a = None if a is None else a.detach().float().contiguous()
+            b = None if b is None else b.detach().float().contiguous()
+            keep += [r, d, gt, gd, a, b]
+            table[i] = nat.SgrMetricFrame(r.data_ptr(), gt.data_ptr(), d.data_ptr(), gd.data_ptr(), nat.ptr(a), nat.ptr(b))
+        nat.check(lib.sgr_render_metrics(len(table), table, C, H, W, float(global_scale), out[3 * c0:].data_ptr(), scratch.data_ptr(),
+                                         scratch_bytes, stream), "sgr_render_metrics")
+    vals = out.view(n, 3).cpu().double()            # the one copy to the host
+    psnr_l, ssim_l, depth_l = (vals[:, j].tolist() for j in range(3))
+    return {"psnr": psnr_l, "ssim": ssim_l, "depth_l1": depth_l, "mean_psnr": float(np.mean(psnr_l)),
+            "mean_ssim": float(np.mean(ssim_l)), "mean_depthl1": float(np.mean(depth_l))}

@@ -1,7 +1,9 @@
 """Mapping loss -- mirror of /root/reference/thirdparty/monogs/utils/slam_utils.py:71-119 (SSIM branch off by default,
-/root/reference/configs/splat_slam.yaml:36) plus a fused HIP variant (`sgr_mapping_loss`) with identical values."""
+/root/reference/configs/splat_slam.yaml:36) plus a fused HIP variant (`sgr_mapping_loss`) with identical values, and
+`ssim_native`, the HIP drop-in for loss_utils.ssim (`sgr_ssim` / `sgr_ssim_backward`)."""
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from splat_slam_amd import _native as nat
 
@@ -35,6 +37,63 @@ def ssim(img1, img2, window_size=11):
     s1, s2, s12 = blur(img1 * img1) - mu1_sq, blur(img2 * img2) - mu2_sq, blur(img1 * img2) - mu12
     c1, c2 = 0.01 ** 2, 0.03 ** 2
     return (((2 * mu12 + c1) * (2 * s12 + c2)) / ((mu1_sq + mu2_sq + c1) * (s1 + s2 + c2))).mean()
+
+
+class _SsimNative(torch.autograd.Function):
+    """The HIP SSIM (sgr_ssim / sgr_ssim_backward): per-image means, fixed-order sums; the forward keeps the three per-pixel
+    derivative maps when img1 needs a gradient, the backward blurs them (no host sync: the upstream is read on the device)."""
+
+    @staticmethod
+    def forward(ctx, img1, img2):
+        lib = nat.lib()
+        x, y = img1.contiguous(), img2.contiguous()
+        B, C, H, W = x.shape if x.dim() == 4 else (1,) + tuple(x.shape)
+        dev = x.device
+        n = B * C * H * W
+        want = ctx.needs_input_grad[0]
+        scratch_bytes = lib.sgr_ssim_scratch_bytes(B, C, H, W)
+        # one arena per call: per-image SSIM | (3 derivative maps) | partials
+        nmaps = 3 * n if want else 0
+        arena = torch.empty(B + nmaps + scratch_bytes // 4, dtype=torch.float32, device=dev)
+        out, maps, scratch = arena[:B], arena[B:B + nmaps], arena[B + nmaps:]
+        if dev.index is not None and dev.index != torch.cuda.current_device():
+            torch.cuda.set_device(dev)
+        nat.check(lib.sgr_ssim(B, C, H, W, x.data_ptr(), y.data_ptr(), out.data_ptr(), maps.data_ptr() if want else None,
+                               scratch.data_ptr(), scratch_bytes, torch.cuda.current_stream().cuda_stream), "sgr_ssim")
+        if want:
+            ctx.save_for_backward(x, y, maps)
+        ctx.dims = (B, C, H, W)
+        return out[0] if B == 1 else out.mean()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, y, maps = ctx.saved_tensors
+        B, C, H, W = ctx.dims
+        g = g.to(dtype=torch.float32).contiguous()
+        dx = torch.empty_like(x)
+        nat.check(nat.lib().sgr_ssim_backward(B, C, H, W, x.data_ptr(), y.data_ptr(), maps.data_ptr(), g.data_ptr(), 0, 1.0 / B,
+                                              dx.data_ptr(), torch.cuda.current_stream().cuda_stream), "sgr_ssim_backward")
+        return dx, None
+
+
+def ssim_native(img1, img2, window_size=11, size_average=True):
+    """loss_utils.ssim (/root/reference/thirdparty/gaussian_splatting/utils/loss_utils.py:61-101) on the HIP kernels, for [C,H,W] and
+    [B,C,H,W] fp32 GPU tensors: the mean of the SSIM map over B*C*H*W, differentiable in img1 (once).  Raises on what it does not
+    implement (another window, size_average=False, non-fp32 input, a gradient for img2) and on CPU tensors: there is no fallback."""
+    if window_size != 11:
+        raise ValueError(f"ssim_native: window_size {window_size} (only 11 is implemented)")
+    if not size_average:
+        raise ValueError("ssim_native: size_average=False is not implemented")
+    if img1.dtype != torch.float32 or img2.dtype != torch.float32:
+        raise TypeError(f"ssim_native: fp32 inputs only ({img1.dtype}, {img2.dtype})")
+    if img1.shape != img2.shape or img1.dim() not in (3, 4) or img1.numel() == 0:
+        raise ValueError(f"ssim_native: [C,H,W] or [B,C,H,W] pairs of one shape ({tuple(img1.shape)}, {tuple(img2.shape)})")
+    if img2.requires_grad:
+        raise ValueError("ssim_native differentiates img1 only (ssim(image, gt_image)); img2 requires grad")
+    if not (img1.is_cuda and img2.is_cuda) or img1.device != img2.device:
+        raise RuntimeError("ssim_native needs GPU tensors on one device (HIP only, no CPU fallback)")
+    return _SsimNative.apply(img1, img2)
 
 
 def uses_ssim(mapping_config):

@@ -167,3 +167,12 @@ class MappingSession:
             self.loop.final_refine(iters=iters)
         frames = [self.loop.viewpoints[k] for k in sorted(self.loop.viewpoints)]
         return eval_rendering_psnr(frames, self.loop.gaussians, PipelineParams(), self.loop.background)
+
+    def evaluate(self, gt_depths=None, global_scale=1.0):
+        """eval_rendering (eval_utils.py:64-197, called at slam.py:153,193) over the session's keyframes in keyframe order: per-frame
+        and mean PSNR, SSIM and depth L1 (splat_slam_amd.eval.eval_rendering)."""
+        from splat_slam_amd.eval import eval_rendering
+        from splat_slam_amd.mapper import PipelineParams
+        frames = [self.loop.viewpoints[k] for k in sorted(self.loop.viewpoints)]
+        return eval_rendering(frames, self.loop.gaussians, PipelineParams(), self.loop.background, gt_depths=gt_depths,
+                              global_scale=global_scale)
