@@ -31,6 +31,10 @@
  *   sgr_map_views          -> the per-view body of Mapper.map (src/mapper.py:426-490): render, loss, backward for <= 16 views
  *   sgr_map_step           -> one iteration of Mapper.map / initialize_map / final_refine (src/mapper.py:303-353, 414-568, 656-708)
  *   sgr_map_run            -> a run of such iterations between two densify / reset points (the `for` loops at :304, :414, :656)
+ *   sgr_ssim_term_bytes,
+ *   sgr_mapping_loss_ssim,
+ *   sgr_map_step_ssim,
+ *   sgr_map_run_ssim       -> the same with the ssim_loss: True mapping loss, thirdparty/monogs/utils/slam_utils.py:89-105
  *   sgr_deform_points      -> Mapper.update_mapping_points, src/mapper.py:154-255
  *   sgr_keep_list,
  *   sgr_gather_rows        -> prune_points / _prune_optimizer and the row selects of densify_and_clone,
@@ -460,6 +464,31 @@ typedef struct SgrMapRun {
                                    pool entries' `ws` are then ignored. */
 } SgrMapRun;
 int sgr_map_run(const SgrMapRun* run, void* stream);
+
+/* The mapping loss with the SSIM term (`ssim_loss: True`, thirdparty/monogs/utils/slam_utils.py:89-105; lambda = opt_params.lambda_dssim):
+ *   L = alpha mean_{c,p}[(1 - lambda) |m (x - gt)| + lambda (1 - ssim(x, gt))] + (1 - alpha) mean_p |md (depth - gt_depth)|
+ * with x = exp(a) image + b (image itself with NULL exposures), SSIM on the raw x (no clamp, no mask).  Per batch of views: one
+ * launch pair (moments and derivative maps; blurred maps -> float dL/dimage, dL/ddepth and the partial sums), then the usual
+ * fixed-order final sum.  No float atomics: bitwise reproducible.
+ * SgrSsimTerm.arena (sgr_ssim_term_bytes(max_views, H, W), device) holds the derivative maps of up to max_views views at a time
+ * and the partial sums of one view; its contents need not survive between calls.
+ * sgr_mapping_loss_ssim: the standalone loss of one [3,H,W] view, gradients times `upstream` (like sgr_mapping_loss).
+ * sgr_map_step_ssim / sgr_map_run_ssim: sgr_map_step / sgr_map_run with this loss.  Every view must render its image, depth and
+ * opacity (SgrOutputs without NULLs), its loss_scratch must hold 3 * ceil(H/16) * ceil(W/32) records of 16 B, and dL_dimage
+ * receives the FLOAT gradient [3,H,W].  term == NULL is exactly sgr_map_step / sgr_map_run. */
+typedef struct SgrSsimTerm {
+  float lambda_dssim;
+  int32_t max_views;            /* views whose maps the arena holds at once (a batch runs in groups of this many) */
+  void* arena;
+  size_t arena_bytes;
+} SgrSsimTerm;
+size_t sgr_ssim_term_bytes(int32_t max_views, int32_t H, int32_t W);
+int sgr_mapping_loss_ssim(int32_t H, int32_t W, const float* image, const float* depth, const float* gt_image,
+                          const float* gt_depth, const float* exposure_a, const float* exposure_b, float alpha,
+                          float rgb_boundary_threshold, float upstream, const SgrSsimTerm* term, float* loss,
+                          float* dL_dimage, float* dL_ddepth, float* dL_dexp_a, float* dL_dexp_b, void* stream);
+int sgr_map_step_ssim(const SgrMapStep* step, const SgrSsimTerm* term, void* stream);
+int sgr_map_run_ssim(const SgrMapRun* run, const SgrSsimTerm* term, void* stream);
 
 /* Adam on a small slab with a per-row switch: row r (width `row_width`) is updated iff active[r] != 0, using its own
  * step counter step[r] (incremented in place).  The exposure parameters of the keyframe optimiser

@@ -98,6 +98,10 @@ class SgrMetricFrame(C.Structure):
     _fields_ = [("render", _fp), ("gt_image", _fp), ("depth", _fp), ("gt_depth", _fp), ("exposure_a", _fp), ("exposure_b", _fp)]
 
 
+class SgrSsimTerm(C.Structure):
+    _fields_ = [("lambda_dssim", C.c_float), ("max_views", C.c_int32), ("arena", _fp), ("arena_bytes", C.c_size_t)]
+
+
 class SgrRowTensor(C.Structure):
     _fields_ = [("in_", _fp), ("out", _fp), ("row_bytes", C.c_int32)]
 
@@ -142,6 +146,11 @@ SIGNATURES = {
                                 C.c_float, C.c_float, C.c_int32, _fp]),
     "sgr_map_step": (C.c_int, [C.POINTER(SgrMapStep), _fp]),
     "sgr_map_run": (C.c_int, [C.POINTER(SgrMapRun), _fp]),
+    "sgr_ssim_term_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "sgr_mapping_loss_ssim": (C.c_int, [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, C.c_float, C.c_float, C.c_float,
+                                        C.POINTER(SgrSsimTerm), _fp, _fp, _fp, _fp, _fp, _fp]),
+    "sgr_map_step_ssim": (C.c_int, [C.POINTER(SgrMapStep), C.POINTER(SgrSsimTerm), _fp]),
+    "sgr_map_run_ssim": (C.c_int, [C.POINTER(SgrMapRun), C.POINTER(SgrSsimTerm), _fp]),
     "sgr_masked_adam": (C.c_int, [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp, C.c_float, C.c_float, C.c_float,
                                   C.c_float, _fp]),
     "sgr_deform_points": (C.c_int, [C.c_int64, _fp, C.POINTER(SgrDeformFrame), _fp, _fp, _fp, _fp]),

@@ -348,13 +348,32 @@ int sgr_backward_views(int32_t num_views, const SgrBackwardView* views, const Sg
 // sinks need not be zero on entry).  Only the fused gather pass can store; whenever a batch does not take it (pose gradients asked
 // for, heterogeneous views, more than kMaxViews) the accumulating passes run instead -- onto sinks that are zeroed HERE first, so
 // that the promise holds on every path (it used to add this iteration's sums to the previous iteration's leftovers).
+// term: the mapping loss with the SSIM term (sgr_map_step_ssim): the tiles composite plainly, the loss runs as its own launch
+// pair over the rendered images (groups of term->max_views views) and leaves float pixel gradients; NULL = the L1 epilogue.
 static int map_views_impl(int32_t num_views, const SgrMapView* views, const SgrInputs* in, const SgrGradInputs* grads, float alpha,
                           float rgb_boundary_threshold, int32_t forward_only, FusedAdam* fused, bool* fused_done,
-                          void* stream, bool store_sinks = false) {
+                          void* stream, bool store_sinks = false, const SgrSsimTerm* term = nullptr) {
   if (fused_done) *fused_done = false;
   if (num_views < 0 || (num_views > 0 && (!views || !in)) || (!forward_only && !grads))
     return set_error(SGR_ERR_INVALID, "map_views: null argument");
   if (num_views == 0) return SGR_OK;
+  if (forward_only) term = nullptr;
+  if (term) {
+    if (!term->arena || term->max_views <= 0)
+      return set_error(SGR_ERR_INVALID, "map_views: SSIM term without an arena");
+    for (int v = 0; v < num_views; ++v) {
+      const SgrMapView& m = views[v];
+      const int H = m.settings.image_height, W = m.settings.image_width;
+      if (!m.out.color || !m.out.depth || !m.out.opacity)
+        return set_error(SGR_ERR_INVALID, "map_views: the SSIM loss needs every view's rendered image, depth and opacity");
+      if (term->arena_bytes < sgr_ssim_term_bytes(term->max_views, H, W))
+        return set_error(SGR_ERR_WORKSPACE, "map_views: SSIM arena too small (need %zu for %d views of %dx%d)",
+                         sgr_ssim_term_bytes(term->max_views, H, W), term->max_views, W, H);
+      if (!m.loss_scratch || m.loss_scratch_bytes < (size_t)ssim_loss_nparts(H, W) * sizeof(LossPart))
+        return set_error(SGR_ERR_WORKSPACE, "map_views: loss_scratch too small for the SSIM loss (need %zu)",
+                         (size_t)ssim_loss_nparts(H, W) * sizeof(LossPart));
+    }
+  }
   hipStream_t st = (hipStream_t)stream;
   // batched execution needs one Layout (same N, H, W, capacity), the same view-independent settings and private scratch
   bool uniform = true;
@@ -389,11 +408,18 @@ static int map_views_impl(int32_t num_views, const SgrMapView* views, const SgrI
         return set_error(SGR_ERR_INVALID, "map_views: outputs may only be omitted in uniform batches");
       if (int rc = sgr_forward(&mv.settings, in, &mv.out, &mv.ws, nullptr, stream)) return rc;
       if (forward_only) continue;
-      if (int rc = sgr_mapping_loss(mv.settings.image_height, mv.settings.image_width, mv.out.color, mv.out.depth, mv.gt_image,
-                                    mv.gt_depth, mv.exposure_a, mv.exposure_b, alpha, rgb_boundary_threshold, 1.0f, mv.loss,
-                                    mv.dL_dimage, mv.dL_ddepth, mv.dL_dexposure, mv.dL_dexposure ? mv.dL_dexposure + 1 : nullptr,
-                                    mv.loss_scratch, mv.loss_scratch_bytes, stream))
+      if (term) {
+        if (int rc = sgr_mapping_loss_ssim(mv.settings.image_height, mv.settings.image_width, mv.out.color, mv.out.depth, mv.gt_image,
+                                           mv.gt_depth, mv.exposure_a, mv.exposure_b, alpha, rgb_boundary_threshold, 1.0f, term,
+                                           mv.loss, mv.dL_dimage, mv.dL_ddepth, mv.dL_dexposure,
+                                           mv.dL_dexposure ? mv.dL_dexposure + 1 : nullptr, stream))
+          return rc;
+      } else if (int rc = sgr_mapping_loss(mv.settings.image_height, mv.settings.image_width, mv.out.color, mv.out.depth, mv.gt_image,
+                                           mv.gt_depth, mv.exposure_a, mv.exposure_b, alpha, rgb_boundary_threshold, 1.0f, mv.loss,
+                                           mv.dL_dimage, mv.dL_ddepth, mv.dL_dexposure, mv.dL_dexposure ? mv.dL_dexposure + 1 : nullptr,
+                                           mv.loss_scratch, mv.loss_scratch_bytes, stream)) {
         return rc;
+      }
       SgrGradOutputs go = {mv.dL_dimage, mv.dL_ddepth};
       SgrGradInputs gi = *grads;
       gi.dL_dtau = mv.dL_dtau;
@@ -444,20 +470,32 @@ static int map_views_impl(int32_t num_views, const SgrMapView* views, const SgrI
     LossCoef lc = {alpha / (3.f * (float)HW), (1.f - alpha) / (float)HW, rgb_boundary_threshold};
     // forward, loss and backward of a tile run in the same wave (one launch) unless the option is off (profiling the two
     // halves separately, bitwise A/B tests)
-    const bool fused_blend = g_opt[SGR_OPT_FUSED_BLEND] != 0 && blend_can_fuse(d);
-    if (fused_blend) launch_blend_fused(tab, nv, d, f.settings.bg, lt, lc, st);
-    else launch_blend_fwd(tab, nv, d, f.settings.bg, &lt, &lc, st);
+    const bool fused_blend = !term && g_opt[SGR_OPT_FUSED_BLEND] != 0 && blend_can_fuse(d);
+    int nparts = L.ntiles;
+    if (term) {        // SSIM: plain compositing, then the loss over the images (the window needs neighbouring tiles)
+      const int H = f.settings.image_height, W = f.settings.image_width;
+      launch_blend_fwd(tab, nv, d, f.settings.bg, nullptr, nullptr, st);
+      for (int g0 = 0; g0 < nv; g0 += term->max_views)
+        launch_ssim_mapping_loss(lt, g0, nv - g0 < term->max_views ? nv - g0 : term->max_views, H, W, alpha, term->lambda_dssim,
+                                 rgb_boundary_threshold, 1.f, (float*)term->arena, st);
+      nparts = ssim_loss_nparts(H, W);
+    } else if (fused_blend) {
+      launch_blend_fused(tab, nv, d, f.settings.bg, lt, lc, st);
+    } else {
+      launch_blend_fwd(tab, nv, d, f.settings.bg, &lt, &lc, st);
+    }
     const bool fuse = fused && num_views <= kMaxViews;
     if (fuse) {        // the loss sums (and the exposure step that consumes them) ride in the optimiser launch
-      fused->tail_views = nv; fused->tail_nparts = L.ntiles;
+      fused->tail_views = nv; fused->tail_nparts = nparts;
       fused->tail_inv_rgb = 1.f / (3.f * (float)HW); fused->tail_inv_dep = 1.f / (float)HW; fused->tail_alpha = alpha;
       for (int v = 0; v < nv; ++v) {
         fused->tail_parts[v] = lt.parts[v]; fused->tail_loss[v] = lt.loss[v]; fused->tail_da[v] = lt.da[v]; fused->tail_db[v] = lt.db[v];
       }
     } else {
-      launch_mapping_loss_final(lt, nv, HW, L.ntiles, alpha, st);
+      launch_mapping_loss_final(lt, nv, HW, nparts, alpha, st);
     }
-    if (!fused_blend) launch_blend_bwd(tab, nv, d, f.settings.bg, &lt, &lc, st);
+    if (term) launch_blend_bwd(tab, nv, d, f.settings.bg, nullptr, nullptr, st);      // float pixel gradients
+    else if (!fused_blend) launch_blend_bwd(tab, nv, d, f.settings.bg, &lt, &lc, st);
     launch_preprocess_bwd(tab, nv, d, cm, *in, *grads, fuse ? fused : nullptr, st, /*mapping_loop=*/true);
     if (fuse && fused_done) *fused_done = true;
   }
@@ -476,7 +514,8 @@ int sgr_map_views(int32_t num_views, const SgrMapView* views, const SgrInputs* i
 
 // One iteration.  When the Adam step directly follows the views of a uniform single-chunk batch and the gradient sinks
 // are the optimiser's own gradient buffers, gather + Adam + next activations run as ONE pass (gather_adam_kernel).
-static int map_step_impl(const SgrMapStep* p, bool skip_activate, bool grads_clean, bool allow_fuse, bool* fused_out, void* stream) {
+static int map_step_impl(const SgrMapStep* p, bool skip_activate, bool grads_clean, bool allow_fuse, bool* fused_out, void* stream,
+                         const SgrSsimTerm* term = nullptr) {
   if (fused_out) *fused_out = false;
   if (!p) return set_error(SGR_ERR_INVALID, "map_step: null argument");
   // an optimiser-only step (no views: the second half of a multi-GPU iteration, after the all-reduce) writes the
@@ -541,7 +580,7 @@ static int map_step_impl(const SgrMapStep* p, bool skip_activate, bool grads_cle
   bool fused = false;
   if (p->num_views > 0)
     if (int rc = map_views_impl(p->num_views, p->views, p->in, p->grads, p->alpha, p->rgb_boundary_threshold, p->forward_only,
-                                try_fuse ? &fa : nullptr, &fused, stream, p->grads_clean == -3 && !p->adam_groups))
+                                try_fuse ? &fa : nullptr, &fused, stream, p->grads_clean == -3 && !p->adam_groups, term))
       return rc;
   if (p->adam_groups && !fused)
     if (int rc = gaussian_adam_step_act(p->num_gaussians, p->adam_groups, p->beta1, p->beta2, p->eps, p->iso_weight,
@@ -564,7 +603,14 @@ int sgr_map_step(const SgrMapStep* p, void* stream) {
   return map_step_impl(p, false, p->grads_clean > 0, p->grads_clean >= 0, nullptr, stream);
 }
 
-int sgr_map_run(const SgrMapRun* r, void* stream) {
+int sgr_map_step_ssim(const SgrMapStep* p, const SgrSsimTerm* term, void* stream) {
+  if (!p) return set_error(SGR_ERR_INVALID, "map_step: null argument");
+  return map_step_impl(p, false, p->grads_clean > 0, p->grads_clean >= 0, nullptr, stream, term);
+}
+
+}  // extern "C"
+
+static int map_run_impl(const SgrMapRun* r, const SgrSsimTerm* term, void* stream) {
   if (!r || r->num_iters < 0 || r->num_window < 0 || r->picks_per_iter < 0 || (r->num_window > 0 && !r->window) ||
       (r->picks_per_iter > 0 && (!r->pool || !r->picks || r->pool_size <= 0)))
     return set_error(SGR_ERR_INVALID, "map_run: bad argument");
@@ -618,12 +664,17 @@ int sgr_map_run(const SgrMapRun* r, void* stream) {
     // after a fused tail the activations of the updated parameters are already written and the sinks are clean
     bool fused = false;
     if (int rc = map_step_impl(&st, prev_fused, it == 0 ? r->step.grads_clean > 0 : r->adam_groups != nullptr, r->step.grads_clean >= 0,
-                               &fused, stream))
+                               &fused, stream, term))
       return rc;
     prev_fused = fused;
   }
   return SGR_OK;
 }
+
+extern "C" {
+
+int sgr_map_run(const SgrMapRun* r, void* stream) { return map_run_impl(r, nullptr, stream); }
+int sgr_map_run_ssim(const SgrMapRun* r, const SgrSsimTerm* term, void* stream) { return map_run_impl(r, term, stream); }
 
 int sgr_query_stats(const SgrWorkspace* ws, int32_t N, int32_t H, int32_t W, const int32_t* radii, int64_t stats_host[4],
                     void* stream) {

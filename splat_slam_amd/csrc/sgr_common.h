@@ -320,6 +320,12 @@ void launch_mapping_loss(const LossTab& tab, int nviews, int HW, float alpha, fl
 // second stage only: `nparts` partial sums per view were already written (by blend_fwd's fused loss epilogue)
 void launch_mapping_loss_final(const LossTab& tab, int nviews, int HW, int nparts, float alpha, hipStream_t st);
 struct LossPart { float rgb, dep, da, db; };
+// the mapping loss with the SSIM term (sgr_ssim.hip): views v0 .. v0 + nv of lt, derivative maps in `maps` (nv view slots of
+// ssim_term_view_maps bytes), ssim_loss_nparts(H, W) LossParts per view in lt.parts
+size_t ssim_term_view_maps(int H, int W);
+int ssim_loss_nparts(int H, int W);
+void launch_ssim_mapping_loss(const LossTab& lt, int v0, int nv, int H, int W, float alpha, float lam, float thr, float upstream,
+                              float* maps, hipStream_t st);
 struct LossCoef { float w_rgb, w_dep, thr; };
 
 // ---- Adam constants of one step (host side computes the bias corrections in double like torch.optim.Adam does)

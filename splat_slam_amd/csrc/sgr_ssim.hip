@@ -301,6 +301,116 @@ __global__ void __launch_bounds__(kSsimThreads) metrics_final_kernel(int nparts,
   }
 }
 
+// ---- the mapping loss with the SSIM term (slam_utils.py:89-105, ssim_loss: True) of a group of views: grid (tiles, 3, views)
+//   L = alpha mean_{c,p} [(1 - lam) |m r| + lam (1 - ssim(x, gt))] + (1 - alpha) mean_p |md (d - gd)|,   x = exp(a) I + b
+// Pass A writes the three derivative maps of the SSIM mean and LossPart.rgb of its (tile, channel); pass B blurs the maps, forms
+// dL/dx, and writes dL/dimage, dL/ddepth and LossPart.{dep, da, db}.  parts[v][c tiles + tile] is one LossPart: launch_mapping_loss_final
+// (or the fused Adam tail) adds them up exactly as it does for the L1 epilogue's per-8x8-tile records.
+namespace {
+__device__ __forceinline__ float exposed(float ea, float I, float eb) { return __builtin_fmaf(ea, I, eb); }   // same bits in A and B
+__device__ __forceinline__ bool rgb_mask(const float* gt, size_t HW, int o, float thr) { return (gt[o] + gt[HW + o]) + gt[2 * HW + o] > thr; }
+__device__ __forceinline__ float sign_of(float r) { return r > 0.f ? 1.f : (r < 0.f ? -1.f : 0.f); }
+}  // namespace
+
+__global__ void __launch_bounds__(kSsimThreads) ssimloss_moments_kernel(LossTab lt, int v0, int H, int W, float lam, float thr,
+                                                                        float scale, float* __restrict__ maps, size_t map_stride) {
+  __shared__ float in[2 * kSsimIH * kSsimIW];
+  __shared__ float hor[5 * kSsimIH * kSsimTW];
+  __shared__ float red[4];
+  const int vw = v0 + blockIdx.z, c = blockIdx.y;
+  const int tiles_x = (W + kSsimTW - 1) / kSsimTW;
+  const int tx0 = (blockIdx.x % tiles_x) * kSsimTW, ty0 = (blockIdx.x / tiles_x) * kSsimTH;
+  const size_t HW = (size_t)H * W;
+  const float* I = lt.image[vw] + c * HW;
+  const float* gt = lt.gt_image[vw];
+  const float* y = gt + c * HW;
+  const float ea = lt.exp_a[vw] ? __expf(lt.exp_a[vw][0]) : 1.f;
+  const float eb = lt.exp_b[vw] ? lt.exp_b[vw][0] : 0.f;
+  tile_load<2>(in, ty0, tx0, H, W, [&](int o, float* v) { v[0] = exposed(ea, I[o], eb); v[1] = y[o]; });
+  __syncthreads();
+  tile_hblur<2, 5>(in, hor, Moments5());
+  __syncthreads();
+  float* mp = maps + (size_t)blockIdx.z * map_stride + c * HW;     // [3 maps][3 channels][H W] per view
+  float acc[1] = {0.f};
+  for (int p = threadIdx.x; p < kSsimTH * kSsimTW; p += kSsimThreads) {
+    const int ty = p / kSsimTW, tx = p % kSsimTW, gy = ty0 + ty, gx = tx0 + tx;
+    if (gy >= H || gx >= W) continue;
+    float m[5], d[3];
+    tile_vblur<5>(hor, ty, tx, m);
+    const float S = ssim_pixel(m, scale, d);
+    const int o = gy * W + gx;
+    mp[o] = d[0];
+    mp[3 * HW + o] = d[1];
+    mp[6 * HW + o] = d[2];
+    const int ci = (ty + kSsimR) * kSsimIW + tx + kSsimR;
+    const float r = rgb_mask(gt, HW, o, thr) ? in[ci] - in[kSsimIH * kSsimIW + ci] : 0.f;
+    acc[0] += (1.f - lam) * fabsf(r) + lam * (1.f - S);
+  }
+  block_partial<1>(acc, red, (float*)((LossPart*)lt.parts[vw] + (size_t)c * gridDim.x + blockIdx.x));
+}
+
+// dL/dx = w_l1 sign(m r) + u (G*dm + 2 x G*d11 + y G*d12), w_l1 = upstream alpha (1 - lam) / (3 H W), u = -upstream alpha lam
+__global__ void __launch_bounds__(kSsimThreads) ssimloss_grad_kernel(LossTab lt, int v0, int H, int W, float w_l1, float w_dep,
+                                                                     float u, float thr, const float* __restrict__ maps,
+                                                                     size_t map_stride) {
+  __shared__ float in[3 * kSsimIH * kSsimIW];
+  __shared__ float hor[3 * kSsimIH * kSsimTW];
+  __shared__ float red[4 * 3];
+  const int vw = v0 + blockIdx.z, c = blockIdx.y;
+  const int tiles_x = (W + kSsimTW - 1) / kSsimTW;
+  const int tx0 = (blockIdx.x % tiles_x) * kSsimTW, ty0 = (blockIdx.x / tiles_x) * kSsimTH;
+  const size_t HW = (size_t)H * W;
+  const float* mp = maps + (size_t)blockIdx.z * map_stride + c * HW;
+  tile_load<3>(in, ty0, tx0, H, W, [&](int o, float* v) { v[0] = mp[o]; v[1] = mp[3 * HW + o]; v[2] = mp[6 * HW + o]; });
+  __syncthreads();
+  tile_hblur<3, 3>(in, hor, Identity3());
+  __syncthreads();
+  const float* I = lt.image[vw] + c * HW;
+  const float* gt = lt.gt_image[vw];
+  float* __restrict__ dimage = lt.dimage[vw];
+  float* __restrict__ ddepth = lt.ddepth[vw];
+  const float ea = lt.exp_a[vw] ? __expf(lt.exp_a[vw][0]) : 1.f;
+  const float eb = lt.exp_b[vw] ? lt.exp_b[vw][0] : 0.f;
+  const bool with_depth = c == 0;                 // the depth term rides in the channel-0 workgroups
+  float acc[3] = {0.f, 0.f, 0.f};                 // dep, da, db
+  for (int p = threadIdx.x; p < kSsimTH * kSsimTW; p += kSsimThreads) {
+    const int ty = p / kSsimTW, tx = p % kSsimTW, gy = ty0 + ty, gx = tx0 + tx;
+    if (gy >= H || gx >= W) continue;
+    float g[3];
+    tile_vblur<3>(hor, ty, tx, g);
+    const int o = gy * W + gx;
+    const float Iv = I[o], x = exposed(ea, Iv, eb), yv = gt[c * HW + o];
+    const float r = rgb_mask(gt, HW, o, thr) ? x - yv : 0.f;
+    const float dab = w_l1 * sign_of(r) + ssim_grad_pixel(g, x, yv, u);   // dL/d(image_ab)
+    if (dimage) dimage[c * HW + o] = dab * ea;
+    acc[1] += dab * ea * Iv;
+    acc[2] += dab;
+    if (with_depth) {
+      const float gd = lt.gt_depth[vw][o];
+      const float rd = gd > 0.01f ? lt.depth[vw][o] - gd : 0.f;
+      acc[0] += fabsf(rd);
+      if (ddepth) ddepth[o] = w_dep * sign_of(rd);
+    }
+  }
+  block_partial<3>(acc, red, (float*)((LossPart*)lt.parts[vw] + (size_t)c * gridDim.x + blockIdx.x) + 1);
+}
+
+size_t ssim_term_view_maps(int H, int W) { return ((size_t)9 * H * W * sizeof(float) + 255) & ~(size_t)255; }
+int ssim_loss_nparts(int H, int W) { return 3 * ssim_tiles(H, W); }
+
+// views v0 .. v0 + nv of `lt` (nv <= the arena's view slots); parts[v] needs ssim_loss_nparts(H, W) LossParts
+void launch_ssim_mapping_loss(const LossTab& lt, int v0, int nv, int H, int W, float alpha, float lam, float thr, float upstream,
+                              float* maps, hipStream_t st) {
+  const int tiles = ssim_tiles(H, W);
+  const float inv_rgb = 1.f / (3.f * (float)H * (float)W), inv_dep = 1.f / ((float)H * (float)W);
+  const size_t stride = ssim_term_view_maps(H, W) / sizeof(float);
+  hipLaunchKernelGGL(ssimloss_moments_kernel, dim3(tiles, 3, nv), dim3(kSsimThreads), 0, st, lt, v0, H, W, lam, thr, inv_rgb, maps,
+                     stride);
+  hipLaunchKernelGGL(ssimloss_grad_kernel, dim3(tiles, 3, nv), dim3(kSsimThreads), 0, st, lt, v0, H, W,
+                     upstream * alpha * (1.f - lam) * inv_rgb, upstream * (1.f - alpha) * inv_dep, -upstream * alpha * lam, thr,
+                     (const float*)maps, stride);
+}
+
 }  // namespace sgr
 
 using namespace sgr;
@@ -310,6 +420,34 @@ extern "C" {
 size_t sgr_ssim_scratch_bytes(int32_t B, int32_t C, int32_t H, int32_t W) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
   return (size_t)B * C * ssim_tiles(H, W) * kMetricParts * sizeof(float);
+}
+
+size_t sgr_ssim_term_bytes(int32_t max_views, int32_t H, int32_t W) {
+  if (max_views <= 0 || H <= 0 || W <= 0) return 0;
+  const size_t parts = ((size_t)ssim_loss_nparts(H, W) * sizeof(LossPart) + 255) & ~(size_t)255;
+  return (size_t)max_views * ssim_term_view_maps(H, W) + parts;
+}
+
+int sgr_mapping_loss_ssim(int32_t H, int32_t W, const float* image, const float* depth, const float* gt_image,
+                          const float* gt_depth, const float* exposure_a, const float* exposure_b, float alpha,
+                          float rgb_boundary_threshold, float upstream, const SgrSsimTerm* term, float* loss,
+                          float* dL_dimage, float* dL_ddepth, float* dL_dexp_a, float* dL_dexp_b, void* stream) {
+  if (H <= 0 || W <= 0 || H > 65535 * kSsimTH || !image || !depth || !gt_image || !gt_depth || !term)
+    return set_error(SGR_ERR_INVALID, "mapping_loss_ssim: null/size");
+  if (!term->arena || term->max_views <= 0 || term->arena_bytes < sgr_ssim_term_bytes(term->max_views, H, W))
+    return set_error(SGR_ERR_WORKSPACE, "mapping_loss_ssim: SSIM arena too small (need %zu for %d views)",
+                     sgr_ssim_term_bytes(term->max_views > 0 ? term->max_views : 1, H, W), term->max_views);
+  // arena: max_views map slots, then the partial records of ONE view (the batched entry points keep theirs in loss_scratch)
+  float* maps = (float*)term->arena;
+  LossTab tab = {};
+  tab.image[0] = image; tab.depth[0] = depth; tab.gt_image[0] = gt_image; tab.gt_depth[0] = gt_depth;
+  tab.exp_a[0] = exposure_a; tab.exp_b[0] = exposure_b; tab.loss[0] = loss; tab.dimage[0] = dL_dimage;
+  tab.ddepth[0] = dL_ddepth; tab.da[0] = dL_dexp_a; tab.db[0] = dL_dexp_b;
+  tab.parts[0] = (char*)term->arena + (size_t)term->max_views * ssim_term_view_maps(H, W);
+  hipStream_t st = (hipStream_t)stream;
+  launch_ssim_mapping_loss(tab, 0, 1, H, W, alpha, term->lambda_dssim, rgb_boundary_threshold, upstream, maps, st);
+  launch_mapping_loss_final(tab, 1, H * W, ssim_loss_nparts(H, W), alpha, st);
+  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "mapping_loss_ssim launch failed");
 }
 
 int sgr_ssim(int32_t B, int32_t C, int32_t H, int32_t W, const float* img1, const float* img2, float* ssim_out, float* maps,

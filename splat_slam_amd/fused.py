@@ -280,14 +280,23 @@ def estimate_pairs(hints, uid, n_now):
 
 
 class FusedMappingLoop(MappingLoop):
-    def __init__(self, config, device="cuda:0", knn_fn=None, check_every=50, span_calls=True):
+    def __init__(self, config, device="cuda:0", knn_fn=None, check_every=50, span_calls=True, native_ssim=False):
         super().__init__(config, device=device, fused_loss=True, knn_fn=knn_fn)
         # `ssim_loss: True` (slam_utils.py:89-98, off by default) is not a per-pixel L1: the fused tile kernel's loss epilogue does
-        # not apply, and the three loops run as the autograd MappingLoop (drop-in rasterizer + torch loss) instead
+        # not apply.  native_ssim=True keeps the loops fused: every view renders its images and the loss runs as the SSIM launch
+        # pair of the _ssim entry points (sgr_map_step_ssim / sgr_map_run_ssim); otherwise the three loops run as the autograd
+        # MappingLoop (drop-in rasterizer + torch loss).
         # `spherical_harmonics: True` (mapper.py:78,85: sh_degree 3, off and "not tested" upstream, splat_slam.yaml:59) gives the map a
-        # [N, 15, 3] f_rest group the fused optimiser pass has no rows for: same fallback (the rasterizer itself handles SH 0-3)
+        # [N, 15, 3] f_rest group the fused optimiser pass has no rows for: the autograd fallback (the rasterizer itself handles SH 0-3)
         from splat_slam_amd.losses import uses_ssim
-        self.autograd_fallback = uses_ssim(config["mapping"]) or bool(config["mapping"]["Training"].get("spherical_harmonics", False))
+        sh = bool(config["mapping"]["Training"].get("spherical_harmonics", False))
+        ssim = uses_ssim(config["mapping"])
+        self.autograd_fallback = (ssim and not native_ssim) or sh
+        self.native_ssim = ssim and native_ssim and not sh
+        self._ssim_lambda = float(config["mapping"]["opt_params"]["lambda_dssim"]) if self.native_ssim else None
+        self._ssim_arena = None      # derivative maps of up to ssim_group views (sgr_ssim_term_bytes), scratch of every SSIM launch
+        self._ssim_term = None
+        self.ssim_group = 16         # views whose maps the arena holds at once (kMaxViews: a batched launch is one group)
         self.lib = nat.lib()
         self.check_every = check_every
         self.fuse_tail = True            # gather + Adam + next activations in one pass (single GPU, regular iterations)
@@ -364,6 +373,9 @@ class FusedMappingLoop(MappingLoop):
                      "allreduce": one all-reduce of the flat gradient buffer, replicated Adam."""
         from splat_slam_amd.parallel import Comm
         assert sync in ("zero1", "allreduce")
+        if self.native_ssim and int(world) > 1:
+            raise NotImplementedError("native_ssim=True runs on one GPU: the multi-GPU iteration of set_parallel has no SSIM "
+                                      "loss stage; use native_ssim=False (the autograd loop) or world=1")
         self.world, self.rank, self.split_views, self.sync = int(world), int(rank), bool(split_views), sync
         self.comm = comm if comm is not None else Comm()
         self._acc_key = None            # buffers are laid out per world size
@@ -377,6 +389,22 @@ class FusedMappingLoop(MappingLoop):
 
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _term(self, cams):
+        """The SgrSsimTerm of a call that renders `cams` (None without native SSIM): its arena grows to the largest image."""
+        if not self.native_ssim:
+            return None
+        need = max([self.lib.sgr_ssim_term_bytes(self.ssim_group, int(c.image_height), int(c.image_width)) for c in cams] or [0])
+        if self._ssim_arena is None or self._ssim_arena.numel() < need:
+            self._ssim_arena = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+            self._ssim_term = nat.SgrSsimTerm(self._ssim_lambda, self.ssim_group, self._ssim_arena.data_ptr(), self._ssim_arena.numel())
+        return C.byref(self._ssim_term)
+
+    def _map_step_call(self, st, cams):
+        term = self._term(cams)
+        if term is None:
+            return self.lib.sgr_map_step(C.byref(st), self._stream())
+        return self.lib.sgr_map_step_ssim(C.byref(st), term, self._stream())
 
     def _ensure_state(self):
         gm = self.gaussians
@@ -712,7 +740,9 @@ class FusedMappingLoop(MappingLoop):
     def _map_view(self, cam, initialization=False, images=True, slot=False):
         """The cached SgrMapView of a camera: pointers into its persistent buffers, sized for the shared capacity.
         images=False: loss + gradients only (the rendered colour / depth / opacity are not written to HBM).
-        slot=True: a pool entry of a span whose picks render in shared workspace slots: no workspace of its own."""
+        slot=True: a pool entry of a span whose picks render in shared workspace slots: no workspace of its own.
+        With native SSIM every view renders its images (the loss reads them)."""
+        images = images or self.native_ssim
         vb = self._view(cam)
         # (storage addresses, not id()s: an id can be re-used by the object that replaces a freed one -- the exposure parameters are
         #  re-bound to their slab row by attach() / _grow())
@@ -946,7 +976,11 @@ class FusedMappingLoop(MappingLoop):
 
     def _launch_span(self, sp):
         self._clean_flat()
-        rc = self.lib.sgr_map_run(C.byref(sp.run), self._stream())
+        term = self._term(sp.window_cams + sp.pool_cams)
+        if term is None:
+            rc = self.lib.sgr_map_run(C.byref(sp.run), self._stream())
+        else:
+            rc = self.lib.sgr_map_run_ssim(C.byref(sp.run), term, self._stream())
         nat.check(rc, "sgr_map_run")
         self.gaussians.invalidate_activations()    # parameters changed through raw pointers: cached torch activations are stale
         self._acc_clean = True
@@ -1073,7 +1107,7 @@ class FusedMappingLoop(MappingLoop):
         else:
             if not forward_only:
                 self._clean_flat()
-            rc = self.lib.sgr_map_step(C.byref(st), self._stream())
+            rc = self._map_step_call(st, cams)
         if not activate:
             st.scaling, st.rotation, st.opacity = sc, ro, op
         nat.check(rc, "sgr_map_step")

@@ -194,3 +194,66 @@ def get_loss_mapping_fused(config, image, depth, viewpoint, opacity, initializat
         import diff_gaussian_rasterization as drg
         return ext.mapping_loss(image, depth, a, b, gt_image, gt_depth, float(alpha), float(thr), bool(drg.DEFER_POSE_GRADS))
     return _FusedMappingLoss.apply(image, depth, a, b, gt_image.contiguous(), gt_depth, float(alpha), float(thr))
+
+
+class _SsimMappingLoss(torch.autograd.Function):
+    """The mapping loss with the SSIM term (sgr_mapping_loss_ssim): loss value + dL/dimage, dL/ddepth, dL/da, dL/db in one launch pair
+    and a fixed-order reduction; the gradients are computed in the forward and scaled by the upstream in the backward."""
+
+    @staticmethod
+    def forward(ctx, image, depth, exp_a, exp_b, gt_image, gt_depth, alpha, thr, lam):
+        lib = nat.lib()
+        dev = image.device
+        _, H, W = image.shape
+        image, depth = image.contiguous(), depth.contiguous()
+        hw = H * W
+        # one arena per call: dL/dimage | dL/ddepth | d/da, d/db | loss | the SSIM term's maps and partial sums
+        term_bytes = lib.sgr_ssim_term_bytes(1, H, W)
+        arena = torch.empty(4 * hw + 4 + (term_bytes + 3) // 4, dtype=torch.float32, device=dev)
+        d_img, d_dep = arena[:3 * hw].view(3, H, W), arena[3 * hw:4 * hw].view(depth.shape)
+        d_a, d_b, loss = arena[4 * hw:4 * hw + 1], arena[4 * hw + 1:4 * hw + 2], arena[4 * hw + 2:4 * hw + 3]
+        maps = arena[4 * hw + 4:]
+        term = nat.SgrSsimTerm(float(lam), 1, maps.data_ptr(), term_bytes)
+        if dev.index is not None and dev.index != torch.cuda.current_device():
+            torch.cuda.set_device(dev)
+        nat.check(lib.sgr_mapping_loss_ssim(H, W, image.data_ptr(), depth.data_ptr(), gt_image.data_ptr(), gt_depth.data_ptr(),
+                                            nat.ptr(exp_a), nat.ptr(exp_b), alpha, thr, 1.0, term, loss.data_ptr(),
+                                            d_img.data_ptr(), d_dep.data_ptr(), d_a.data_ptr(), d_b.data_ptr(),
+                                            torch.cuda.current_stream().cuda_stream), "sgr_mapping_loss_ssim")
+        ctx.save_for_backward(arena[:4 * hw + 2])
+        ctx.has_exp, ctx.shape = exp_a is not None, (H, W, tuple(depth.shape))
+        return loss[0].clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        grads, = ctx.saved_tensors
+        H, W, dshape = ctx.shape
+        hw = H * W
+        s = grads * g                            # the four gradients are contiguous: ONE scaling launch
+        return (s[:3 * hw].view(3, H, W), s[3 * hw:4 * hw].view(dshape), s[4 * hw:4 * hw + 1] if ctx.has_exp else None,
+                s[4 * hw + 1:4 * hw + 2] if ctx.has_exp else None, None, None, None, None, None)
+
+
+def get_loss_mapping_ssim_native(config, image, depth, viewpoint, opacity, initialization=False):
+    """get_loss_mapping (slam_utils.py:71-105) with `ssim_loss: True` on the HIP kernels: (1 - lambda) |masked L1| + lambda (1 - ssim)
+    of the exposure-compensated image, plus the depth L1, differentiable (once) in image, depth and the exposure parameters.  fp32
+    GPU tensors only (no CPU fallback).  With `ssim_loss: False` it is get_loss_mapping_fused."""
+    if not uses_ssim(config):
+        return get_loss_mapping_fused(config, image, depth, viewpoint, opacity, initialization)
+    if image.dtype != torch.float32 or depth.dtype != torch.float32:
+        raise TypeError(f"get_loss_mapping_ssim_native: fp32 image and depth only ({image.dtype}, {depth.dtype})")
+    if not (image.is_cuda and depth.is_cuda):
+        raise RuntimeError("get_loss_mapping_ssim_native needs GPU tensors (HIP only, no CPU fallback)")
+    if image.dim() != 3 or image.shape[0] != 3 or depth.numel() != image.shape[1] * image.shape[2]:
+        raise ValueError(f"get_loss_mapping_ssim_native: image [3,H,W] and depth [1,H,W] ({tuple(image.shape)}, {tuple(depth.shape)})")
+    alpha = config["Training"]["alpha"] if "alpha" in config["Training"] else 0.95
+    thr = config["Training"]["rgb_boundary_threshold"]
+    lam = config["opt_params"]["lambda_dssim"]
+    gt_image = viewpoint.original_image.to(image.device, torch.float32).contiguous()
+    gt_depth = _gt_depth(viewpoint, image.device).contiguous()
+    a, b = (None, None) if initialization else (viewpoint.exposure_a, viewpoint.exposure_b)
+    for t in (a, b):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32):
+            raise TypeError("get_loss_mapping_ssim_native: exposure parameters must be fp32 GPU tensors")
+    return _SsimMappingLoss.apply(image, depth, a, b, gt_image, gt_depth, float(alpha), float(thr), float(lam))
