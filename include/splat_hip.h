@@ -20,6 +20,8 @@
  *                             thirdparty/monogs/utils/slam_utils.py:89-98, imported at src/mapper.py:35) and its autograd backward
  *   sgr_render_metrics     -> the PSNR / SSIM / depth-L1 part of eval_rendering, src/utils/eval_utils.py:90-128, called from
  *                             src/slam.py:153,193
+ *   sgr_tsdf_*, sgr_mesh_* -> the mesh branch of the same function (eval_utils.py:70-74, 142-179: Open3D's ScalableTSDFVolume
+ *                             integrate / extract_triangle_mesh) and clean_mesh (:331-379, trimesh connected components)
  *   sgr_adam_step          -> torch.optim.Adam(eps=1e-15) over the GaussianModel groups,
  *                             thirdparty/gaussian_splatting/scene/gaussian_model.py:264-313, stepped at
  *                             src/mapper.py:352,557,703
@@ -309,6 +311,65 @@ typedef struct SgrMetricFrame {
 } SgrMetricFrame;
 int sgr_render_metrics(int32_t n, const SgrMetricFrame* frames, int32_t C, int32_t H, int32_t W, float global_scale, float* out,
                        void* scratch, size_t scratch_bytes, void* stream);
+
+/* TSDF fusion and mesh extraction of eval_rendering's `mesh` branch (eval_utils.py:70-74, 142-179; clean_mesh :331-379), after
+ * Open3D's ScalableTSDFVolume (RGB8) and trimesh; the conventions are listed in DESIGN.md section 3.
+ * The volume is a hash from unit key (16^3 voxels, unit length 16 * voxel_length) to a pool of units.  Unit u of the pool holds
+ * SGR_TSDF_UNIT_FLOATS floats: five planes of 4096 voxels (tsdf, weight, r, g, b on 0..255), voxel v = x + 16 y + 256 z.
+ * Keys pack floor(p / unit_length) per axis as three 21-bit offset-binary fields (x high), so keys sort as (x, y, z).
+ * `state` (sgr_tsdf_bytes(hash_capacity)) holds the hash, the per-slot frame marks, the touched list and int32 counters:
+ *   counters[0] units allocated (pool indices handed out), [1] != 0: the hash was full, [2] touched-list length,
+ *   [3] != 0: integration met a unit beyond pool_capacity (a caller error).
+ * Per chunk of <= SGR_TSDF_MAX_FRAMES frames: sgr_tsdf_touch (idempotent: it may be re-run after sgr_tsdf_rehash into a larger
+ * hash), then the caller reads the counters once, grows the pool if counters[0] > pool_capacity (pool indices never change:
+ * copy the old pool to the front of a zeroed larger one), and calls sgr_tsdf_integrate with counters[2].  Integration may not
+ * be repeated: weights accumulate. */
+#define SGR_TSDF_UNIT_FLOATS (5 * 4096)
+#define SGR_TSDF_MAX_FRAMES 16
+typedef struct SgrTsdfVolume {
+  float voxel_length;          /* 5/512 in the reference */
+  float sdf_trunc;             /* 0.04 */
+  float depth_trunc;           /* 30: depth above it is dropped (create_from_color_and_depth) */
+  int32_t hash_capacity;       /* power of two, >= 64 */
+  int32_t pool_capacity;       /* units */
+  void* state;                 /* sgr_tsdf_bytes(hash_capacity) */
+  float* pool;                 /* [pool_capacity, SGR_TSDF_UNIT_FLOATS] */
+} SgrTsdfVolume;
+typedef struct SgrTsdfFrame {
+  const float* render;         /* [3,H,W] rendered colour */
+  const float* depth;          /* [H,W] rendered depth */
+  const float* gt_depth;       /* [H,W]: depth is dropped where it is 0; or NULL */
+  const float* exposure_a;     /* device scalar, or NULL (colour = clamp(exp(a) render + b, 0, 1), truncated to 0..255) */
+  const float* exposure_b;     /* device scalar, or NULL */
+  float fx, fy, cx, cy;
+  float w2c[16];               /* host, row-major world -> camera */
+  float global_scale;          /* depth = global_scale * rendered depth */
+} SgrTsdfFrame;
+size_t sgr_tsdf_bytes(int32_t hash_capacity);
+int sgr_tsdf_reset(const SgrTsdfVolume* vol, void* stream);                       /* empty hash, zero counters and pool */
+int sgr_tsdf_rehash(const SgrTsdfVolume* src, const SgrTsdfVolume* dst, void* stream);   /* dst: reset, larger; marks dropped */
+int sgr_tsdf_touch(const SgrTsdfVolume* vol, int32_t n, const SgrTsdfFrame* frames, int32_t H, int32_t W, void* stream);
+int sgr_tsdf_integrate(const SgrTsdfVolume* vol, int32_t n, const SgrTsdfFrame* frames, int32_t H, int32_t W, int32_t n_touched,
+                       void* stream);
+/* Marching cubes over the n_units allocated units (counters[0]) in ascending key order: sgr_tsdf_extract_count writes
+ * totals[0..1] = (vertices, triangles) on the device; sgr_tsdf_extract then writes vertices [V,3], colours [V,3] (0..1) and
+ * triangles [F,3] with the same scratch.  Vertices are ordered by (unit key, voxel, edge x/y/z), triangles by (unit key, cube,
+ * table order). */
+size_t sgr_tsdf_extract_bytes(int32_t hash_capacity, int32_t pool_capacity);
+int sgr_tsdf_extract_count(const SgrTsdfVolume* vol, int32_t n_units, void* scratch, size_t scratch_bytes, int32_t* totals,
+                           void* stream);
+int sgr_tsdf_extract(const SgrTsdfVolume* vol, int32_t n_units, void* scratch, size_t scratch_bytes, float* vertices,
+                     float* colors, int32_t* triangles, void* stream);
+/* clean_mesh: connected components over triangle edges (label = smallest vertex id of the component), components of at least
+ * min_len vertices kept; then faces with a repeated index or zero area and repeated faces (same vertex set; the first is kept)
+ * dropped.  sgr_mesh_components writes totals[0..1] = kept (vertices, triangles); sgr_mesh_compact writes them in their original
+ * order, reindexed, and vertex_map[V] (new index or -1) when not NULL. */
+size_t sgr_mesh_bytes(int32_t V, int32_t F);
+int sgr_mesh_components(int32_t V, int32_t F, const float* vertices, const int32_t* triangles, int32_t min_len, void* scratch,
+                        size_t scratch_bytes, int32_t* totals, void* stream);
+int sgr_mesh_compact(int32_t V, int32_t F, const float* vertices, const float* colors, const int32_t* triangles, void* scratch,
+                     size_t scratch_bytes, float* out_vertices, float* out_colors, int32_t* out_triangles, int32_t* vertex_map,
+                     void* stream);
 
 /* One torch.optim.Adam step (no weight decay, no amsgrad) on a flat parameter slab. step = the value AFTER
  * increment (1 on the first call).  lr may differ per call (update_learning_rate, gaussian_model.py:315-329). */

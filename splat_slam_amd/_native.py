@@ -102,6 +102,20 @@ class SgrSsimTerm(C.Structure):
     _fields_ = [("lambda_dssim", C.c_float), ("max_views", C.c_int32), ("arena", _fp), ("arena_bytes", C.c_size_t)]
 
 
+class SgrTsdfVolume(C.Structure):
+    _fields_ = [("voxel_length", C.c_float), ("sdf_trunc", C.c_float), ("depth_trunc", C.c_float), ("hash_capacity", C.c_int32),
+                ("pool_capacity", C.c_int32), ("state", _fp), ("pool", _fp)]
+
+
+class SgrTsdfFrame(C.Structure):
+    _fields_ = [("render", _fp), ("depth", _fp), ("gt_depth", _fp), ("exposure_a", _fp), ("exposure_b", _fp), ("fx", C.c_float),
+                ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("w2c", C.c_float * 16), ("global_scale", C.c_float)]
+
+
+SGR_TSDF_UNIT_FLOATS = 5 * 4096
+SGR_TSDF_MAX_FRAMES = 16
+
+
 class SgrRowTensor(C.Structure):
     _fields_ = [("in_", _fp), ("out", _fp), ("row_bytes", C.c_int32)]
 
@@ -135,6 +149,18 @@ SIGNATURES = {
     "sgr_ssim_backward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_int32, C.c_float, _fp, _fp]),
     "sgr_render_metrics": (C.c_int, [C.c_int32, C.POINTER(SgrMetricFrame), C.c_int32, C.c_int32, C.c_int32, C.c_float, _fp, _fp,
                                      C.c_size_t, _fp]),
+    "sgr_tsdf_bytes": (C.c_size_t, [C.c_int32]),
+    "sgr_tsdf_reset": (C.c_int, [C.POINTER(SgrTsdfVolume), _fp]),
+    "sgr_tsdf_rehash": (C.c_int, [C.POINTER(SgrTsdfVolume), C.POINTER(SgrTsdfVolume), _fp]),
+    "sgr_tsdf_touch": (C.c_int, [C.POINTER(SgrTsdfVolume), C.c_int32, C.POINTER(SgrTsdfFrame), C.c_int32, C.c_int32, _fp]),
+    "sgr_tsdf_integrate": (C.c_int, [C.POINTER(SgrTsdfVolume), C.c_int32, C.POINTER(SgrTsdfFrame), C.c_int32, C.c_int32,
+                                     C.c_int32, _fp]),
+    "sgr_tsdf_extract_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "sgr_tsdf_extract_count": (C.c_int, [C.POINTER(SgrTsdfVolume), C.c_int32, _fp, C.c_size_t, _fp, _fp]),
+    "sgr_tsdf_extract": (C.c_int, [C.POINTER(SgrTsdfVolume), C.c_int32, _fp, C.c_size_t, _fp, _fp, _fp, _fp]),
+    "sgr_mesh_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "sgr_mesh_components": (C.c_int, [C.c_int32, C.c_int32, _fp, _fp, C.c_int32, _fp, C.c_size_t, _fp, _fp]),
+    "sgr_mesh_compact": (C.c_int, [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_size_t, _fp, _fp, _fp, _fp, _fp]),
     "sgr_adam_step": (C.c_int, [C.c_int64, _fp, _fp, _fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float,
                                 C.c_int64, _fp]),
     "sgr_adam_step_multi": (C.c_int, [C.c_int32, C.POINTER(SgrAdamTensor), C.c_float, C.c_float, C.c_float, C.c_float, _fp]),

@@ -2,8 +2,9 @@
 /root/reference/thirdparty/gaussian_splatting/utils/image_utils.py:19-21), SSIM (the reference's own in-tree
 loss_utils.ssim, thirdparty/gaussian_splatting/utils/loss_utils.py:61-101) and the rendered depth's L1 error.
 `eval_rendering` computes all three on the HIP kernels (sgr_render_metrics); `eval_rendering_psnr` is the PSNR-only
-torch formulation.  LPIPS is not computed: it needs pretrained AlexNet weights from outside the project.  The mesh
-metrics (TSDF fusion, open3d) are out of scope as well."""
+torch formulation.  With mesh=True, eval_rendering also fuses every frame into a TSDF volume and returns the cleaned
+mesh (:70-74, 142-179, clean_mesh :331-379) from the HIP kernels of splat_slam_amd.mesh.  LPIPS is not computed: it needs
+pretrained AlexNet weights from outside the project; the mesh's accuracy against ground-truth meshes is out of scope as well."""
 import numpy as np
 import torch
 
@@ -41,17 +42,24 @@ def _device_depth(d, device):
 
 
 @torch.no_grad()
-def eval_rendering(frames, gaussians, pipe, background, gt_depths=None, global_scale=1.0):
+def eval_rendering(frames, gaussians, pipe, background, gt_depths=None, global_scale=1.0, mesh=False, mesh_path=None, c2w=None,
+                   voxel_length=5.0 / 512.0, sdf_trunc=0.04):
     """eval_rendering's per-frame metrics (eval_utils.py:90-128, means as :190-194) on the HIP kernels: frames is a list of Camera
     in keyframe order; every frame but the first gets its exposure compensation (:96-99), the image is clamped to [0, 1];
     PSNR over the elements where the ground truth is > 0 (:109,123), SSIM of the whole image (:124), depth L1 of
     global_scale * rendered depth over pixels where both depths are > 0 (:116-120).  gt_depths: one [H,W] per frame (default:
     each frame's `depth`).  One copy to the host per call.  A frame without a valid depth pixel gives NaN (the reference's 0/0), a
-    perfect frame PSNR inf.  LPIPS is not computed (module docstring)."""
+    perfect frame PSNR inf.  LPIPS is not computed (module docstring).
+    mesh=True (:70-74, 142-179): each frame's render of the metrics chunk is also fused into a TSDF volume (voxel_length, sdf_trunc,
+    depth_trunc 30) with the exposure-compensated colour and global_scale * rendered depth, dropped where the ground-truth depth is
+    0, at the pose c2w[k] (camera -> world 4x4, the reference's traj_est_aligned; default each frame's own pose).  The result gains
+    "mesh", the cleaned TriangleMesh, written as PLY to mesh_path when given."""
     if not frames:
         raise ValueError("eval_rendering: no frames")
     if gt_depths is not None and len(gt_depths) != len(frames):
         raise ValueError(f"eval_rendering: {len(gt_depths)} ground-truth depths for {len(frames)} frames")
+    if c2w is not None and len(c2w) != len(frames):
+        raise ValueError(f"eval_rendering: {len(c2w)} poses for {len(frames)} frames")
     lib = nat.lib()
     dev = frames[0].original_image.device
     if dev.type != "cuda":
@@ -62,8 +70,14 @@ def eval_rendering(frames, gaussians, pipe, background, gt_depths=None, global_s
     arena = torch.empty(3 * n + scratch_bytes // 4, dtype=torch.float32, device=dev)
     out, scratch = arena[:3 * n], arena[3 * n:]
     stream = torch.cuda.current_stream().cuda_stream
+    volume = poses = None
+    if mesh:
+        from splat_slam_amd.mesh import TSDFVolume
+        volume = TSDFVolume(voxel_length=voxel_length, sdf_trunc=sdf_trunc, depth_trunc=30.0, device=dev)
+        poses = _w2c(frames) if c2w is None else [torch.linalg.inv(torch.as_tensor(p).detach().double().cpu()) for p in c2w]
     for c0 in range(0, n, _METRIC_CHUNK):
         keep, table = [], (nat.SgrMetricFrame * min(_METRIC_CHUNK, n - c0))()
+        fuse = (nat.SgrTsdfFrame * len(table))() if mesh else None
         for i, k in enumerate(range(c0, c0 + len(table))):
             frame = frames[k]
             pkg = render(frame, gaussians, pipe, background)
@@ -77,9 +91,30 @@ def eval_rendering(frames, gaussians, pipe, background, gt_depths=None, global_s
             b = None if b is None else b.detach().float().contiguous()
             keep += [r, d, gt, gd, a, b]
             table[i] = nat.SgrMetricFrame(r.data_ptr(), gt.data_ptr(), d.data_ptr(), gd.data_ptr(), nat.ptr(a), nat.ptr(b))
+            if mesh:
+                pose = poses[k]
+                fuse[i] = nat.SgrTsdfFrame(r.data_ptr(), d.data_ptr(), gd.data_ptr(), nat.ptr(a), nat.ptr(b), float(frame.fx),
+                                           float(frame.fy), float(frame.cx), float(frame.cy),
+                                           (nat.C.c_float * 16)(*[float(x) for x in pose.reshape(-1)]), float(global_scale))
         nat.check(lib.sgr_render_metrics(len(table), table, C, H, W, float(global_scale), out[3 * c0:].data_ptr(), scratch.data_ptr(),
                                          scratch_bytes, stream), "sgr_render_metrics")
+        if mesh:
+            if C != 3:
+                raise ValueError(f"eval_rendering(mesh=True): colour frames must have 3 channels, not {C}")
+            volume._integrate_table(fuse, H, W)
     vals = out.view(n, 3).cpu().double()            # the one copy to the host
     psnr_l, ssim_l, depth_l = (vals[:, j].tolist() for j in range(3))
-    return {"psnr": psnr_l, "ssim": ssim_l, "depth_l1": depth_l, "mean_psnr": float(np.mean(psnr_l)),
-            "mean_ssim": float(np.mean(ssim_l)), "mean_depthl1": float(np.mean(depth_l))}
+    result = {"psnr": psnr_l, "ssim": ssim_l, "depth_l1": depth_l, "mean_psnr": float(np.mean(psnr_l)),
+              "mean_ssim": float(np.mean(ssim_l)), "mean_depthl1": float(np.mean(depth_l))}
+    if mesh:
+        from splat_slam_amd.mesh import clean_mesh
+        result["mesh"] = clean_mesh(volume.extract_triangle_mesh(), min_len=100)
+        if mesh_path is not None:
+            result["mesh"].write_ply(mesh_path)
+    return result
+
+
+def _w2c(frames):
+    """every frame's own world -> camera pose, host fp64, in one copy"""
+    from splat_slam_amd.camera import getWorld2View2
+    return torch.stack([getWorld2View2(f.R, f.T).detach() for f in frames]).double().cpu()
