@@ -16,15 +16,21 @@ iteration, parallelised; gradients meet in one RCCL reduce-scatter, Adam runs on
 an all-gather returns the parameters (ZeRO-1).  value = steps/sec / 61, no factor N.
 --scaling weak: every rank renders its own 12 views (a 12*N-view batch per step); value = N * steps/sec / 61.
 
-Besides the headline the line carries (all measured in this run, outside the headline's timed region):
+A plain run sets up, runs the event-timed kernel legs below (they are the iterations before the --warmup steps, so every run's
+timed steps start from the same state), warms up, times the steps, writes --dump-outputs and prints the line.  Besides the headline
+it carries (measured outside the headline's timed region):
   roofline            the fused tile kernel (forward + loss + backward of a tile in one wave): the dominant kernel of the timed loop
   roofline_unfused_blend_bwd   blend_bwd_kernel<true> -- the north-star kernel -- event-timed with the tile kernels UN-fused
+  work_per_view       visible Gaussians, (tile, Gaussian) pairs and walked-list lengths per view
+With --full the run then measures everything else (each trimmed by its own --no-* / --refine-iters option):
+  roofline.traffic    HBM bytes and VALU issue of the two tile kernels from rocprofv3 --pmc child passes of this command
+  render_ms, refine_iterations_per_s   single-view render timings and the final_refine rate (N > 1: `refine`, over the ranks)
   extra.session       40 tracker frames of the configs[1] session (MappingSession, default hyper-parameters): ms per keyframe, PSNR
   extra.session_full  the WHOLE configs[1] session (160 tracker frames once around the room): final map size, wall
                       ms per mapped keyframe / keyframes per s, PSNR over all keyframes, HIP- vs oracle-rendered PSNR of the final map
   dropin_keyframes_per_s   the same map() iteration through the drop-in autograd API (GaussianRasterizer per view, reference
                       loop structure intact, torch.optim.Adam)
-  extra.opaque_scene  the same N with log-scale + 1.6: a converged, surface-covering map (long per-tile lists)
+  extra.opaque_scene  the same N with log-scale + 1.6: a converged, surface-covering map (long per-tile lists); roofline_opaque
   cpu_baseline        the oracle on the host cores, one view of the same scene
 
 Prints ONE JSON line (rank 0).
@@ -36,6 +42,7 @@ import os
 import sys
 import time
 
+T_START = time.perf_counter()          # (SPLAT_BENCH_TRACE times its messages from here: torch's import included)
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -51,7 +58,7 @@ HIST_BINS = ["0", "1-4", "5-8", "9-16", "17-32", "33-64", "65-256", ">256"]
 
 def trace(msg):
     if os.environ.get("SPLAT_BENCH_TRACE"):
-        print("[trace]", msg, file=sys.stderr, flush=True)
+        print("[trace] %.2f s" % (time.perf_counter() - T_START), msg, file=sys.stderr, flush=True)
 
 
 def parse():
@@ -71,6 +78,10 @@ def parse():
     ap.add_argument("--order", default="random", choices=["random", "keyframe"],
                     help="order of the Gaussians in memory: random (worst case for the forward's per-segment view test) or the "
                          "order a SLAM session produces (keyframe after keyframe)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure everything else the module docstring lists (PMC child passes, render and "
+                         "refine timings, CPU baseline, drop-in / session / scene legs); --no-pmc, --refine-iters 0, --no-cpu-baseline "
+                         "and --no-extras leave out their part")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the drop-in and opaque-scene legs")
     ap.add_argument("--refine-iters", type=int, default=200, help="final_refine iterations timed for refine it/s (0 = skip)")
@@ -131,7 +142,7 @@ def dry_run(args):
         print(json.dumps({"metric": "mapping frames/sec + render ms @640x480, 300k Gaussians; PSNR vs ref", "value": None, "dry_run": True,
                           "n_gpus": world, "ranks_seen": int(seen.item()), "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": round(1e3 * float(t.item()) / max(1, args.steps), 6),
-                          "scaling": args.scaling if world > 1 else "none", "scaling_when_sharded": args.scaling}))
+                          "scaling": args.scaling if world > 1 else "none", "scaling_when_sharded": args.scaling, "full": args.full}))
     if world > 1:
         dist.destroy_process_group()
 
@@ -638,9 +649,9 @@ def main():
         "host_enqueue_ms_per_step": round(1e3 * host_issue / args.steps, 4), "settle_iterations_untimed": args.settle,
         "iterations_before_timed_region": untimed,
         "map_iterations_per_s": round(args.steps / elapsed, 2),
-        "world_size_seen": (B.dist.get_world_size() if B.dist is not None else 1), "transport": B.transport,
+        "world_size_seen": (B.dist.get_world_size() if B.dist is not None else 1), "transport": B.transport, "full": args.full,
     }
-    if world > 1 and args.loop == "fused" and args.refine_iters > 0:
+    if args.full and world > 1 and args.loop == "fused" and args.refine_iters > 0:
         # configs[4]: global map refinement over the ranks (mapper.py:656-708 with one random view per RANK and optimiser step,
         # ZeRO-1 exchange) -- renders/s of the whole job; --refine-views 1 times the reference's single-view step, replicated
         g = world if args.refine_views == "world" else int(args.refine_views)
@@ -668,6 +679,11 @@ def main():
         # `roofline_unfused_blend_bwd` = the north-star's kernel as a stand-alone launch (SGR_OPT_FUSED_BLEND = 0 leg of this run);
         # `roofline_fused` stays as an alias of `roofline` so that earlier rounds' readers find it
         out["roofline"], out["roofline_unfused_blend_bwd"], out["roofline_fused"] = roof_f, roof_bwd, roof_f
+        if not args.full:
+            for roof in (roof_f, roof_bwd):
+                roof["traffic_source"] = "not measured: the PMC child passes run with --full; " + roof["traffic_source"]
+    # ---- --full: everything besides the headline line's own keys (a plain run ends here)
+    if args.full and args.loop == "fused" and world == 1:
         if not args.no_pmc:
             pass_args = ["--gaussians", str(N), "--camera", args.camera, "--views", str(args.views), "--scale-add", str(args.scale_add),
                          "--order", args.order]

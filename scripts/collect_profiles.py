@@ -114,9 +114,9 @@ for name in ("kernel_batched_avg", "pmc_hbm_bytes"):       # what bench.py quote
     shutil.copy(os.path.join(out, tag + "_" + name + ".json"), os.path.join(out, "latest_" + name + ".json"))
     shutil.copy(os.path.join(out, tag + "_" + name + ".json"), os.path.join(ROOT, "profiles", "latest_" + name + ".json"))
 
-# ---- 3. the plain bench line (defaults), for tests/test_bench_contract.py and BASELINE.md -- LAST, so that its `roofline.traffic`
-# is quoted from the PMC passes above
-r0 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")], cwd=ROOT, env=env, capture_output=True, text=True)
+# ---- 3. the full bench line (defaults + --full), for tests/test_bench_contract.py and BASELINE.md -- LAST, so that its
+# `roofline.traffic` is quoted from the PMC passes above
+r0 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"], cwd=ROOT, env=env, capture_output=True, text=True)
 line = [l for l in r0.stdout.splitlines() if l.startswith("{")]
 if line:
     open(os.path.join(out, tag + "_bench_line.json"), "w").write(line[-1] + "\n")

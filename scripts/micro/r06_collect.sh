@@ -16,7 +16,7 @@ python scripts/run_session_config1.py --oracle-views 2 --out $OUT/${TAG}_session
 tail -c 600 $OUT/session.log
 python scripts/multi_path_time.py --kernels --out $OUT/${TAG}_multi_path_time_light.json > $OUT/multi.log 2>&1
 tail -4 $OUT/multi.log
-python bench.py --gaussians 1500000 --no-extras --no-cpu-baseline > $OUT/${TAG}_bench_1500k.json 2> $OUT/b1500.err
+python bench.py --gaussians 1500000 --full --no-extras --no-cpu-baseline > $OUT/${TAG}_bench_1500k.json 2> $OUT/b1500.err
 python scripts/table_numbers.py > $OUT/table.log 2>&1; cp gpurun_out/table_numbers.json $OUT/${TAG}_table_numbers.json
 python scripts/profile_dropin.py --out $OUT/${TAG}_dropin_phases.json > $OUT/dropin.log 2>&1
 tail -3 $OUT/dropin.log

@@ -34,7 +34,7 @@ def psnr_vs_oracle(n, camera):
 
 rows = []
 for name, n, cam in CONFIGS:
-    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gaussians", str(n), "--camera", cam, "--no-extras"]
+    args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gaussians", str(n), "--camera", cam, "--full", "--no-extras"]
     if n > 20000:
         args.append("--no-cpu-baseline")
     out = subprocess.run(args, capture_output=True, text=True).stdout

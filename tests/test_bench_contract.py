@@ -1,4 +1,4 @@
-"""The JSON line bench.py printed on the MI355X (committed under profiles/) carries every key of the driver's contract."""
+"""The JSON line `bench.py --full` printed on the MI355X (committed under profiles/) carries every key of the driver's contract."""
 import glob
 import json
 import os

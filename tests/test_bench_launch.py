@@ -29,3 +29,8 @@ def test_gpus_1_runs_in_process():
     d = _run("--gpus", "1", "--dry-run", "--steps", "2", "--scaling", "weak")
     # one rank scales nothing: the label says so; the mode the flags select is reported next to it
     assert d["n_gpus"] == 1 and d["ranks_seen"] == 1 and d["scaling"] == "none" and d["scaling_when_sharded"] == "weak"
+
+
+def test_full_is_off_by_default_and_reported():
+    assert _run("--dry-run", "--steps", "1")["full"] is False
+    assert _run("--dry-run", "--steps", "1", "--full")["full"] is True

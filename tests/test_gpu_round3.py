@@ -322,7 +322,7 @@ def test_final_refine_one_view_per_rank_replicas_bitwise_and_equal_to_single_pro
 def test_bench_gpus_2_starts_two_ranks_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--gaussians", "20000", "--camera", "tiny", "--steps",
-                        "6", "--warmup", "2", "--no-extras", "--no-cpu-baseline", "--refine-iters", "8"],
+                        "6", "--warmup", "2", "--full", "--no-extras", "--no-cpu-baseline", "--refine-iters", "8"],
                        capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
