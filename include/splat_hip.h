@@ -22,6 +22,10 @@
  *                             src/slam.py:153,193
  *   sgr_tsdf_*, sgr_mesh_* -> the mesh branch of the same function (eval_utils.py:70-74, 142-179: Open3D's ScalableTSDFVolume
  *                             integrate / extract_triangle_mesh) and clean_mesh (:331-379, trimesh connected components)
+ *   sgr_surface_sample*, sgr_nn_*, sgr_icp_accumulate, sgr_cloud_metrics, sgr_eval_reduce_bytes
+ *                          -> the eval_mesh branch of the same function (eval_utils.py:174-187: run_evaluation of
+ *                             evaluate_3d_reconstruction_lib, distance_thresh 0.05, icp_align=True): surface sampling, exact nearest
+ *                             neighbours, point-to-point ICP sums and the accuracy / completion reductions
  *   sgr_adam_step          -> torch.optim.Adam(eps=1e-15) over the GaussianModel groups,
  *                             thirdparty/gaussian_splatting/scene/gaussian_model.py:264-313, stepped at
  *                             src/mapper.py:352,557,703
@@ -370,6 +374,33 @@ int sgr_mesh_components(int32_t V, int32_t F, const float* vertices, const int32
 int sgr_mesh_compact(int32_t V, int32_t F, const float* vertices, const float* colors, const int32_t* triangles, void* scratch,
                      size_t scratch_bytes, float* out_vertices, float* out_colors, int32_t* out_triangles, int32_t* vertex_map,
                      void* stream);
+
+/* Mesh evaluation of eval_rendering's eval_mesh branch (eval_utils.py:174-187: run_evaluation(pred_ply, ..., distance_thresh=0.05,
+ * icp_align=True) of evaluate_3d_reconstruction_lib, whose conventions are assumed as listed in DESIGN.md section 3).
+ * sgr_surface_sample: n points drawn uniformly by area from the mesh (fp64 areas and CDF; the uniforms are a hash of (seed, sample
+ * index), so the output does not depend on the launch shape), points [n,3] and the face of each [n]; *total_area (device, may be
+ * NULL) receives the mesh's area.  Faces of zero area are never picked.  n = 0 only computes the area. */
+size_t sgr_surface_sample_bytes(int32_t F);
+int sgr_surface_sample(int32_t V, int32_t F, const float* vertices, const int32_t* triangles, int32_t n, uint64_t seed, void* scratch,
+                       size_t scratch_bytes, float* points, int32_t* tri_idx, double* total_area, void* stream);
+/* Exact nearest neighbours: sgr_nn_grid_build sorts the n target points (transformed by the host 3x4 row-major matrix `transform`
+ * when not NULL) into a uniform grid held in `grid` (sgr_nn_grid_bytes(n) bytes, caller-owned, built once, queried many times).
+ * sgr_nn_query: for each of the nq query points (transformed on the fly by `transform` when not NULL) dist = Euclidean distance to
+ * the nearest target point and idx = its index (ties: the smallest index); where that distance exceeds max_dist (INFINITY: no
+ * limit) dist = INFINITY and idx = -1. */
+size_t sgr_nn_grid_bytes(int32_t n);
+int sgr_nn_grid_build(int32_t n, const float* points, const float* transform, void* grid, size_t grid_bytes, void* stream);
+int sgr_nn_query(int32_t n, const void* grid, size_t grid_bytes, int32_t nq, const float* query, const float* transform, float max_dist,
+                 float* dist, int32_t* idx, void* stream);
+/* Fixed-order fp64 reductions (per-workgroup partials in `scratch` of sgr_eval_reduce_bytes() bytes, then one ordered pass; no
+ * float atomics).  sgr_icp_accumulate: over the sources with idx >= 0, p = transform * source (as sgr_nn_query forms it) and
+ * q = target[idx]: sums[17] = count, sum |p - q|^2, sum p (3), sum q (3), sum p q^T (9, row-major).  sgr_cloud_metrics:
+ * out[4] = sum dist_a, #(dist_a < thresh), sum dist_b, #(dist_b < thresh). */
+size_t sgr_eval_reduce_bytes(void);
+int sgr_icp_accumulate(int32_t n, const float* source, const float* transform, const int32_t* idx, int32_t n_target, const float* target,
+                       double* sums, void* scratch, size_t scratch_bytes, void* stream);
+int sgr_cloud_metrics(int32_t na, const float* dist_a, int32_t nb, const float* dist_b, float thresh, double* out, void* scratch,
+                      size_t scratch_bytes, void* stream);
 
 /* One torch.optim.Adam step (no weight decay, no amsgrad) on a flat parameter slab. step = the value AFTER
  * increment (1 on the first call).  lr may differ per call (update_learning_rate, gaussian_model.py:315-329). */

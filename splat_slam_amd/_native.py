@@ -161,6 +161,14 @@ SIGNATURES = {
     "sgr_mesh_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "sgr_mesh_components": (C.c_int, [C.c_int32, C.c_int32, _fp, _fp, C.c_int32, _fp, C.c_size_t, _fp, _fp]),
     "sgr_mesh_compact": (C.c_int, [C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, C.c_size_t, _fp, _fp, _fp, _fp, _fp]),
+    "sgr_surface_sample_bytes": (C.c_size_t, [C.c_int32]),
+    "sgr_surface_sample": (C.c_int, [C.c_int32, C.c_int32, _fp, _fp, C.c_int32, C.c_uint64, _fp, C.c_size_t, _fp, _fp, _fp, _fp]),
+    "sgr_nn_grid_bytes": (C.c_size_t, [C.c_int32]),
+    "sgr_nn_grid_build": (C.c_int, [C.c_int32, _fp, C.POINTER(C.c_float), _fp, C.c_size_t, _fp]),
+    "sgr_nn_query": (C.c_int, [C.c_int32, _fp, C.c_size_t, C.c_int32, _fp, C.POINTER(C.c_float), C.c_float, _fp, _fp, _fp]),
+    "sgr_eval_reduce_bytes": (C.c_size_t, []),
+    "sgr_icp_accumulate": (C.c_int, [C.c_int32, _fp, C.POINTER(C.c_float), _fp, C.c_int32, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "sgr_cloud_metrics": (C.c_int, [C.c_int32, _fp, C.c_int32, _fp, C.c_float, _fp, _fp, C.c_size_t, _fp]),
     "sgr_adam_step": (C.c_int, [C.c_int64, _fp, _fp, _fp, _fp, C.c_float, C.c_float, C.c_float, C.c_float,
                                 C.c_int64, _fp]),
     "sgr_adam_step_multi": (C.c_int, [C.c_int32, C.POINTER(SgrAdamTensor), C.c_float, C.c_float, C.c_float, C.c_float, _fp]),

@@ -3,8 +3,9 @@
 loss_utils.ssim, thirdparty/gaussian_splatting/utils/loss_utils.py:61-101) and the rendered depth's L1 error.
 `eval_rendering` computes all three on the HIP kernels (sgr_render_metrics); `eval_rendering_psnr` is the PSNR-only
 torch formulation.  With mesh=True, eval_rendering also fuses every frame into a TSDF volume and returns the cleaned
-mesh (:70-74, 142-179, clean_mesh :331-379) from the HIP kernels of splat_slam_amd.mesh.  LPIPS is not computed: it needs
-pretrained AlexNet weights from outside the project; the mesh's accuracy against ground-truth meshes is out of scope as well."""
+mesh (:70-74, 142-179, clean_mesh :331-379) from the HIP kernels of splat_slam_amd.mesh; given a ground-truth mesh it also
+scores that mesh (:174-187: accuracy, completion, completion ratio, precision, F-score and chamfer-L1 after ICP alignment) on the
+HIP kernels of splat_slam_amd.mesh_eval.  LPIPS is not computed: it needs pretrained AlexNet weights from outside the project."""
 import numpy as np
 import torch
 
@@ -43,7 +44,8 @@ def _device_depth(d, device):
 
 @torch.no_grad()
 def eval_rendering(frames, gaussians, pipe, background, gt_depths=None, global_scale=1.0, mesh=False, mesh_path=None, c2w=None,
-                   voxel_length=5.0 / 512.0, sdf_trunc=0.04):
+                   voxel_length=5.0 / 512.0, sdf_trunc=0.04, eval_mesh=True, gt_mesh_path=None, distance_thresh=0.05, icp_align=True,
+                   mesh_samples=200_000):
     """eval_rendering's per-frame metrics (eval_utils.py:90-128, means as :190-194) on the HIP kernels: frames is a list of Camera
     in keyframe order; every frame but the first gets its exposure compensation (:96-99), the image is clamped to [0, 1];
     PSNR over the elements where the ground truth is > 0 (:109,123), SSIM of the whole image (:124), depth L1 of
@@ -53,7 +55,11 @@ def eval_rendering(frames, gaussians, pipe, background, gt_depths=None, global_s
     mesh=True (:70-74, 142-179): each frame's render of the metrics chunk is also fused into a TSDF volume (voxel_length, sdf_trunc,
     depth_trunc 30) with the exposure-compensated colour and global_scale * rendered depth, dropped where the ground-truth depth is
     0, at the pose c2w[k] (camera -> world 4x4, the reference's traj_est_aligned; default each frame's own pose).  The result gains
-    "mesh", the cleaned TriangleMesh, written as PLY to mesh_path when given."""
+    "mesh", the cleaned TriangleMesh, written as PLY to mesh_path when given.
+    eval_mesh with a ground-truth mesh gt_mesh_path (a PLY path or a TriangleMesh; :174-187): the result also gains "mesh_metrics",
+    splat_slam_amd.mesh_eval.evaluate_mesh(mesh, gt, distance_thresh, icp_align, samples=mesh_samples), or, where that raises
+    ValueError (e.g. a mesh without a triangle of positive area), "mesh_metrics_error" with its message, as the reference's
+    try/except does.  Without a ground-truth mesh the result is what it is without these arguments."""
     if not frames:
         raise ValueError("eval_rendering: no frames")
     if gt_depths is not None and len(gt_depths) != len(frames):
@@ -111,6 +117,13 @@ def eval_rendering(frames, gaussians, pipe, background, gt_depths=None, global_s
         result["mesh"] = clean_mesh(volume.extract_triangle_mesh(), min_len=100)
         if mesh_path is not None:
             result["mesh"].write_ply(mesh_path)
+        if eval_mesh and gt_mesh_path is not None:
+            from splat_slam_amd.mesh_eval import evaluate_mesh
+            try:
+                result["mesh_metrics"] = evaluate_mesh(result["mesh"], gt_mesh_path, distance_thresh=distance_thresh,
+                                                       icp_align=icp_align, samples=mesh_samples)
+            except ValueError as e:
+                result["mesh_metrics_error"] = str(e)
     return result
 
 
