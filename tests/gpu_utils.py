@@ -212,3 +212,105 @@ def drop_knife_edges_and_depth_ties(inp, s, max_rounds=60):
             if inp.get(k) is not None:
                 inp[k] = inp[k][keep].contiguous()
     raise AssertionError("knife edges / depth ties did not clear after %d rounds (%d of %d Gaussians left)" % (max_rounds, inp["means3D"].shape[0], n0))
+
+
+class HintDriver:
+    """sgr_forward + sgr_backward of one scene through the C ABI with a CHOSEN SgrWorkspace.max_list_hint (the drop-in package picks
+    its own, process-wide hint).  Modelled on FusedMappingLoop._settings / _inputs / _workspace.  inp, s: fp32-exact inputs and
+    settings (tests/list_scenes.py); wc, wd: the loss weights dL/dcolor, dL/ddepth."""
+
+    def __init__(self, inp, s, wc, wd, capacity, dev="cuda:0"):
+        import ctypes as C
+        from splat_slam_amd import _native as nat
+        self.C, self.nat, self.lib, self.dev = C, nat, nat.lib(), dev
+        f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        self.N, self.H, self.W = int(inp["means3D"].shape[0]), int(s.image_height), int(s.image_width)
+        self.t = dict(means3D=f(inp["means3D"]), opac=f(inp["opacities"].reshape(-1)), shs=f(inp["shs"]), scales=f(inp["scales"]),
+                      rot=f(inp["rotations"]), bg=f(s.bg), view=f(s.viewmatrix), full=f(s.projmatrix), raw=f(s.projmatrix_raw),
+                      campos=f(s.campos), wc=f(wc), wd=f(wd))
+        t = self.t
+        st = nat.SgrSettings()
+        st.num_gaussians, st.image_height, st.image_width = self.N, self.H, self.W
+        st.sh_degree, st.sh_coeffs = int(s.sh_degree), int(inp["shs"].shape[1])
+        st.tanfovx, st.tanfovy, st.scale_modifier, st.prefiltered, st.debug = s.tanfovx, s.tanfovy, float(s.scale_modifier), 0, 0
+        st.bg, st.viewmatrix, st.projmatrix = t["bg"].data_ptr(), t["view"].data_ptr(), t["full"].data_ptr()
+        st.projmatrix_raw, st.campos = t["raw"].data_ptr(), t["campos"].data_ptr()
+        self.settings = st
+        self.inputs = nat.SgrInputs(t["means3D"].data_ptr(), t["opac"].data_ptr(), t["shs"].data_ptr(), None, t["scales"].data_ptr(),
+                                    t["rot"].data_ptr(), None)
+        self.cap = int(capacity)
+
+    def tile_lengths(self, saved):
+        """[gy, gx] per-8x8-tile list lengths the forward binned, read from the saved block's tile ranges (start | kOverfull, end)
+        at the offset Layout (csrc/sgr_common.h) carves for them: header, tile counters, one 64-byte record per Gaussian and the
+        point list, each 256-byte aligned.  The caller checks the sum and the maximum against header words 9 and 10."""
+        al = lambda x: (x + 255) // 256 * 256
+        gx, gy = (self.W + 7) // 8, (self.H + 7) // 8
+        o = al(64)                                              # header
+        o = al(o + ((gy + 1) // 2) * ((gx + 1) // 2) * 4 * 8)   # tile counters
+        o = al(o + max(self.N, 1) * 64)                         # records
+        o = al(o + max(self.cap, 1) * 4)                        # point list
+        r = saved[o:o + gx * gy * 16].cpu().view(torch.int32).reshape(gx * gy, 4)[:, :2].long()
+        return (r[:, 1] - (r[:, 0] & 0x7fffffff)).reshape(gy, gx)
+
+    def block(self):
+        """A fresh (saved, scratch) pair: its contents are garbage, so its first forward must pass counters_clean = 0."""
+        sb = self.lib.sgr_saved_bytes(self.N, self.H, self.W, self.cap)
+        tb = self.lib.sgr_scratch_bytes(self.N, self.H, self.W, self.cap)
+        return (torch.empty(sb, dtype=torch.uint8, device=self.dev), torch.empty(tb, dtype=torch.uint8, device=self.dev))
+
+    def run(self, hint, block=None, counters_clean=0, backward="single"):
+        """One forward (synchronous pair count) and its backward on `block` (fresh when None).  Returns a dict of CPU tensors: the
+        five outputs, every gradient and the 16 header words of the forward.  backward: "single" = sgr_backward, "views" =
+        sgr_backward_views with one view (what the drop-in package's collector calls)."""
+        C, nat, lib, t = self.C, self.nat, self.lib, self.t
+        N, H, W = self.N, self.H, self.W
+        assert block is not None or counters_clean == 0, "counters_clean = 1 is only valid on a block that completed a forward"
+        saved, scratch = block if block is not None else self.block()
+        ws = nat.SgrWorkspace(saved.data_ptr(), saved.numel(), scratch.data_ptr(), scratch.numel(), self.cap, int(counters_clean),
+                              int(hint))
+        e = lambda *sh, dt=torch.float32: torch.full(sh, float("nan") if dt == torch.float32 else -7, dtype=dt, device=self.dev)
+        o = dict(color=e(3, H, W), depth=e(1, H, W), opacity=e(1, H, W), radii=e(N, dt=torch.int32), n_touched=e(N, dt=torch.int32))
+        out = nat.SgrOutputs(o["color"].data_ptr(), o["depth"].data_ptr(), o["opacity"].data_ptr(), o["radii"].data_ptr(),
+                             o["n_touched"].data_ptr())
+        stream = torch.cuda.current_stream(self.dev).cuda_stream
+        R = C.c_int64(0)
+        nat.check(lib.sgr_forward(C.byref(self.settings), C.byref(self.inputs), C.byref(out), C.byref(ws), C.byref(R), stream),
+                  "sgr_forward")
+        words = (C.c_uint32 * 16)()
+        nat.check(lib.sgr_query_header(saved.data_ptr(), words, stream), "sgr_query_header")
+        g = dict(means3D=e(N, 3), means2D=e(N, 3), opacities=e(N), shs=e(*t["shs"].shape), scales=e(N, 3), rotations=e(N, 4), tau=e(6))
+        if backward == "single":
+            gi = nat.SgrGradInputs(g["means3D"].data_ptr(), g["means2D"].data_ptr(), g["opacities"].data_ptr(), g["shs"].data_ptr(),
+                                   None, g["scales"].data_ptr(), g["rotations"].data_ptr(), None, g["tau"].data_ptr(), 0, None, None, None)
+            go = nat.SgrGradOutputs(t["wc"].data_ptr(), t["wd"].data_ptr())
+            nat.check(lib.sgr_backward(C.byref(self.settings), C.byref(self.inputs), o["radii"].data_ptr(), C.byref(go), C.byref(gi),
+                                       C.byref(ws), stream), "sgr_backward")
+        else:
+            g["means2D"].zero_()
+            gi = nat.SgrGradInputs(g["means3D"].data_ptr(), None, g["opacities"].data_ptr(), g["shs"].data_ptr(), None,
+                                   g["scales"].data_ptr(), g["rotations"].data_ptr(), None, None, 0, None, None, None)
+            v = nat.SgrBackwardView(self.settings, o["radii"].data_ptr(), ws, t["wc"].data_ptr(), t["wd"].data_ptr(),
+                                    g["means2D"].data_ptr(), g["tau"].data_ptr())
+            nat.check(lib.sgr_backward_views(1, C.byref(v), C.byref(self.inputs), C.byref(gi), stream), "sgr_backward_views")
+        torch.cuda.synchronize(self.dev)
+        res = {k: v.cpu() for k, v in o.items()}
+        res.update({"d_" + k: v.cpu() for k, v in g.items()})
+        res["header"] = [int(x) for x in words]
+        res["tile_lengths"] = self.tile_lengths(saved)
+        res["pairs"] = int(R.value)
+        return res
+
+
+RESULT_KEYS = ("color", "depth", "opacity", "radii", "n_touched", "d_means3D", "d_means2D", "d_opacities", "d_shs", "d_scales",
+               "d_rotations", "d_tau")
+
+
+def assert_bitwise(a, b, what):
+    """Every output and gradient of two HintDriver.run results has the same bits."""
+    for k in RESULT_KEYS:
+        x, y = a[k], b[k]
+        same = x.shape == y.shape and bool((x.contiguous().view(-1).view(torch.int32) == y.contiguous().view(-1).view(torch.int32)).all())
+        if not same:
+            diff = (x.double() - y.double()).abs()
+            raise AssertionError(f"{what}: {k} differs ({int((diff != 0).sum())} elements, max |diff| {diff.max().item():.3g})")

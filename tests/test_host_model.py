@@ -214,35 +214,78 @@ def test_narrow_backward_groups_interleaved_in_their_dpp_row():
             assert {row * gpr + ((p & 15) & (gpr - 1)) for p in partners} == set(range(row * gpr, row * gpr + gpr))
 
 
-def test_tile_of_block_is_a_bijection_and_its_division_is_exact():
-    """csrc/sgr_blend.hip tile_of_block: workgroup b (hardware places it on XCD b % 8) -> 8x8 tile.  Every XCD walks a contiguous run of
-    16x16 super tiles, four tiles each; every tile of the image is owned by exactly one block of the grid 8 * 4 * ceil(nsuper / 8);
-    the division by the super-tile row length is a multiply-high by floor(2^32 / sgx) + 1 (LOff.sgx_magic), exact while
-    st * sgx < 2^32."""
-    for W, H in ((640, 480), (640, 320), (512, 384), (320, 240), (96, 64), (50, 37), (16, 16), (1296, 968), (4000, 3000)):
-        sgx, sgy = (W + 15) // 16, (H + 15) // 16
-        gx, gy = (W + 7) // 8, (H + 7) // 8
-        nsuper = sgx * sgy
-        per = (nsuper + 7) >> 3
-        magic = (1 << 32) // sgx + 1
-        assert nsuper * sgx < 1 << 32
-        owners = {}
-        for b in range(8 * 4 * per):
-            j = b >> 3
-            st, wv = (b & 7) * per + (j >> 2), j & 3
-            if st >= nsuper or j >= 4 * per:
-                continue
-            row = (st * magic) >> 32
-            assert row == st // sgx
+def _tile_grid_model(W, H, N, order=None, backward=False):
+    """csrc/sgr_blend.hip tile_grid / tile_grid_dim / tile_of_block as shipped: grid (32, rows, views) with rows = ceil(nsuper / 8) +
+    ceil(lead / 32), lead = comp_blocks = ceil(ceil(N / 256) / kCompSegs) rounded up to 8; block (x, y): k = (y - lead_rows) * 8 +
+    (x & 7), wv = (x >> 3) & 3.  order: the launch order (tile_order_used) -- st = order[k] for k < nsuper -- or None for the band
+    mapping st = (k & 7) * ceil(nsuper / 8) + (k >> 3), st < nsuper.  backward: blend_bwd_kernel's grid, tile_grid(0) /
+    tile_grid_dim(L, n, 0) -- no lead rows.  Returns ({(tx, ty): (x, y)}, rows, lead_rows, sgx, magic)."""
+    sgx, sgy = (W + 15) // 16, (H + 15) // 16
+    gx, gy = (W + 7) // 8, (H + 7) // 8
+    nsuper = sgx * sgy
+    nseg = (N + 255) // 256
+    lead = 0 if backward else (((nseg + 3) // 4) + 7) & ~7
+    lead_rows = (lead + 31) >> 5
+    rows = (nsuper + 7) // 8 + (lead + 31) // 32
+    magic = ((1 << 32) // sgx + 1) & 0xffffffff
+    owners = {}
+    for y in range(rows):
+        for x in range(32):
+            if y < lead_rows:
+                continue                         # compact_visible_list blocks (y * 32 + x < lead)
+            k, wv = (y - lead_rows) * 8 + (x & 7), (x >> 3) & 3
+            if order is not None:
+                if k >= nsuper:
+                    continue
+                st = order[k]
+            else:
+                st = (k & 7) * ((nsuper + 7) >> 3) + (k >> 3)
+                if st >= nsuper:
+                    continue
+            row = st if sgx == 1 else (st * magic) >> 32
+            assert row == st // sgx, (W, H, st)
             tx, ty = (st - row * sgx) * 2 + (wv & 1), row * 2 + (wv >> 1)
             if tx >= gx or ty >= gy:
-                continue
-            assert (tx, ty) not in owners
-            owners[(tx, ty)] = b
-        assert len(owners) == gx * gy
-        # the four tiles of a super tile sit on ONE XCD, in consecutive slots of its queue
-        for (tx, ty), b in owners.items():
-            assert owners.get((tx ^ 1, ty), b) & 7 == b & 7 and owners.get((tx, ty ^ 1), b) & 7 == b & 7
+                continue                         # (the tile kernels return on tiles beyond the image: partial super tiles)
+            assert (tx, ty) not in owners, (W, H, tx, ty)
+            owners[(tx, ty)] = (x, y)
+    return owners, rows, lead_rows, sgx, magic
+
+
+def test_tile_of_block_is_a_bijection_and_its_division_is_exact():
+    """Both branches of tile_of_block (launch order for any permutation, band mapping), in the forward's grid (lead rows of
+    compact_visible_list blocks first) and the backward's (none): every 8x8 tile is owned by exactly one block
+    of the grid, k >= nsuper (launch order) and st >= nsuper (band) own nothing, the four tiles of a super tile share an XCD (x & 7),
+    the multiply-high by LOff.sgx_magic is the exact division (sgx == 1 takes st itself: 2^32 / 1 + 1 wraps), and gridDim.y stays
+    within 65535."""
+    import random
+    rng = random.Random(3)
+    sizes = ((640, 480), (640, 320), (512, 384), (320, 240), (96, 64), (72, 40), (50, 37), (44, 20), (16, 16), (16, 200), (8, 8),
+             (1296, 968), (4000, 3000), (8192, 4096))
+    for W, H in sizes:
+        sgx, sgy = (W + 15) // 16, (H + 15) // 16
+        nsuper = sgx * sgy
+        assert nsuper * sgx < 1 << 32
+        gx, gy = (W + 7) // 8, (H + 7) // 8
+        perm = list(range(nsuper))
+        rng.shuffle(perm)
+        for N in ((300, 1500000) if nsuper < 20000 else (1500000,)):
+            for order, backward in ((None, False), (list(range(nsuper)), False), (perm, False), (None, True), (perm, True)):
+                owners, rows, lead_rows, sgx_, magic = _tile_grid_model(W, H, N, order, backward)
+                assert len(owners) == gx * gy, (W, H, N)
+                assert rows <= 65535, (W, H, N, rows)
+                nseg = (N + 255) // 256
+                assert lead_rows == 0 if backward else lead_rows * 32 >= (nseg + 3) // 4, (W, H, N)
+                for (tx, ty), (x, y) in owners.items():
+                    for nb in ((tx ^ 1, ty), (tx, ty ^ 1), (tx ^ 1, ty ^ 1)):
+                        if nb in owners:
+                            assert owners[nb][0] & 7 == x & 7 and owners[nb][1] == y, (W, H, tx, ty)
+        if sgx == 1:
+            assert (((1 << 32) // sgx + 1) & 0xffffffff) == 1        # why tile_of_block special-cases it
+        else:
+            magic = (1 << 32) // sgx + 1
+            for st in list(range(min(nsuper, 4096))) + [nsuper - 1]:
+                assert (st * magic) >> 32 == st // sgx
 
 
 def test_g_stash_fits_the_unused_part_of_the_wave_slice():
