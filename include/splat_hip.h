@@ -48,6 +48,8 @@
  *   sgr_query*, sgr_profile_*,
  *   sgr_set_option         -> (no reference counterpart) capacity protocol, work counters, per-kernel HIP-event timing, options
  *   sknn_dist2             -> simple_knn._C.distCUDA2, thirdparty/gaussian_splatting/scene/gaussian_model.py:18,194-200
+ *   sgr_dba_*              -> droid_backends.{ba, frame_distance, projmap, iproj, depth_filter} (thirdparty/glorie_slam/lib/droid.cpp),
+ *                             thirdparty/glorie_slam/depth_video.py:195-204 (frame_distance), :231 (ba), :363 (depth_filter)
  *   se3_*                  -> lietorch SE3 ops used on the mapping path, thirdparty/glorie_slam/depth_video.py:327-330
  *                             (SE3(pose).inv().matrix()), and the tau convention of
  *                             thirdparty/monogs/utils/pose_utils.py:66-98.
@@ -625,6 +627,50 @@ int sgr_gather_rows(int64_t m, const int32_t* src_rows, int32_t num_tensors, con
 /* simple_knn distCUDA2: mean squared distance to the 3 nearest neighbours (self excluded). */
 size_t sknn_scratch_bytes(int32_t n);
 int sknn_dist2(const float* xyz, int32_t n, float* mean_dist2, void* scratch, size_t scratch_bytes, void* stream);
+
+/* Dense bundle adjustment and frame geometry of the tracker (droid_backends).  Poses are [N,7] (t, q xyzw) world -> camera,
+ * disparity maps [N,ht,wd], intrinsics [4] (fx, fy, cx, cy), edge lists int64.  Edges whose frames lie outside both poses and
+ * disps take part in nothing (ba) or give NaN (frame_distance, projmap).
+ * sgr_dba_ba runs `iterations` Gauss-Newton steps in place on poses[t0, t1) and on the disparities of the K frames
+ * kx = sorted unique(ii U [t0, t1)), with no host synchronisation.  dx is [t1-t0, 6] and dz [K, ht*wd] of the last step.  The
+ * window is limited to 512 frames (SGR_ERR_CAPACITY beyond).  A reduced system that is not positive definite gives dx = 0 and the
+ * step goes on.  When K differs from the number of distinct depth frames found on the device, nothing is updated and dx, dz
+ * are NaN.  motion_only solves the pose blocks alone (dz untouched, may be NULL); depth_only leaves the poses as they are. */
+typedef struct SgrDbaProblem {
+  float* poses;                /* [num_poses, 7], updated */
+  int32_t num_poses;
+  float* disps;                /* [num_frames, ht, wd], updated */
+  int32_t num_frames, ht, wd;
+  const float* intrinsics;     /* [4] */
+  const float* disps_sens;     /* [num_frames, ht, wd]: sensor disparity, > 0 where measured */
+  const float* targets;        /* [num_edges, 2, ht, wd] */
+  const float* weights;        /* [num_edges, 2, ht, wd] */
+  const float* eta;            /* [num_depth, ht, wd] */
+  const int64_t* ii;           /* [num_edges] */
+  const int64_t* jj;           /* [num_edges] */
+  int32_t num_edges, num_depth;
+  int32_t t0, t1, iterations;
+  float lm, ep;
+  int32_t motion_only, depth_only;
+  float* dx;                   /* [t1-t0, 6] out */
+  float* dz;                   /* [num_depth, ht*wd] out */
+} SgrDbaProblem;
+size_t sgr_dba_scratch_bytes(int32_t num_frames, int32_t num_edges, int32_t num_depth, int32_t window, int32_t ht, int32_t wd);
+int sgr_dba_ba(const SgrDbaProblem* problem, void* scratch, size_t scratch_bytes, void* stream);
+/* dist [num_edges]; beta weighs the full flow against the translation-only flow */
+int sgr_dba_frame_distance(const float* poses, int32_t num_poses, const float* disps, int32_t num_frames, int32_t ht, int32_t wd,
+                           const float* intrinsics, const int64_t* ii, const int64_t* jj, int32_t num_edges, float beta, float* dist,
+                           void* stream);
+/* coords [num_edges, ht, wd, 3] (third channel 0), valid [num_edges, ht, wd, 1] */
+int sgr_dba_projmap(const float* poses, int32_t num_poses, const float* disps, int32_t num_frames, int32_t ht, int32_t wd,
+                    const float* intrinsics, const int64_t* ii, const int64_t* jj, int32_t num_edges, float* coords, float* valid,
+                    void* stream);
+/* points [num_frames, ht, wd, 3]; poses has at least num_frames rows */
+int sgr_dba_iproj(const float* poses, const float* disps, int32_t num_frames, int32_t ht, int32_t wd, const float* intrinsics,
+                  float* points, void* stream);
+/* counter [num, ht, wd]: neighbours ix-1, ix-2, ix-3, ix+3, ix+4, ix+5 of each ix = inds[b] that agree within thresh[b] */
+int sgr_dba_depth_filter(const float* poses, const float* disps, int32_t num_frames, int32_t ht, int32_t wd, const float* intrinsics,
+                         const int64_t* inds, int32_t num, const float* thresh, float* counter, void* stream);
 
 /* SE3 ops, batched over n.  Pose = (tx,ty,tz,qx,qy,qz,qw) as in lietorch / depth_video.py:69; tau = (rho, theta). */
 int se3_exp(const float* tau, int64_t n, float* pose_out, void* stream);

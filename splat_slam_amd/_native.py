@@ -120,6 +120,17 @@ class SgrRowTensor(C.Structure):
     _fields_ = [("in_", _fp), ("out", _fp), ("row_bytes", C.c_int32)]
 
 
+class SgrDbaProblem(C.Structure):
+    _fields_ = [("poses", _fp), ("num_poses", C.c_int32), ("disps", _fp), ("num_frames", C.c_int32), ("ht", C.c_int32),
+                ("wd", C.c_int32), ("intrinsics", _fp), ("disps_sens", _fp), ("targets", _fp), ("weights", _fp), ("eta", _fp),
+                ("ii", _fp), ("jj", _fp), ("num_edges", C.c_int32), ("num_depth", C.c_int32), ("t0", C.c_int32), ("t1", C.c_int32),
+                ("iterations", C.c_int32), ("lm", C.c_float), ("ep", C.c_float), ("motion_only", C.c_int32),
+                ("depth_only", C.c_int32), ("dx", _fp), ("dz", _fp)]
+
+
+SGR_DBA_MAX_WINDOW = 512
+
+
 # name -> (restype, argtypes); must list every symbol include/splat_hip.h declares (tests/test_abi.py checks)
 SIGNATURES = {
     "sgr_abi_version": (C.c_int, []),
@@ -193,6 +204,13 @@ SIGNATURES = {
     "sgr_gather_rows": (C.c_int, [C.c_int64, _fp, C.c_int32, C.POINTER(SgrRowTensor), _fp]),
     "sknn_scratch_bytes": (C.c_size_t, [C.c_int32]),
     "sknn_dist2": (C.c_int, [_fp, C.c_int32, _fp, _fp, C.c_size_t, _fp]),
+    "sgr_dba_scratch_bytes": (C.c_size_t, [C.c_int32] * 6),
+    "sgr_dba_ba": (C.c_int, [C.POINTER(SgrDbaProblem), _fp, C.c_size_t, _fp]),
+    "sgr_dba_frame_distance": (C.c_int, [_fp, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_int32, C.c_float,
+                                         _fp, _fp]),
+    "sgr_dba_projmap": (C.c_int, [_fp, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_int32, _fp, _fp, _fp]),
+    "sgr_dba_iproj": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp]),
+    "sgr_dba_depth_filter": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, _fp, _fp, _fp]),
     "se3_exp": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_log": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_inv": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
