@@ -1,5 +1,6 @@
 """Drop-in for the `droid_backends` extension of the reference tracker (thirdparty/glorie_slam/lib/droid.cpp), imported by
-thirdparty/glorie_slam/depth_video.py.  Backed by the gfx950 kernels `sgr_dba_*` (include/splat_hip.h, csrc/sgr_dba.hip).
+thirdparty/glorie_slam/depth_video.py and modules/droid_net/corr.py.  Geometry is backed by the gfx950 kernels `sgr_dba_*`
+(include/splat_hip.h, csrc/sgr_dba.hip).
 
     ba(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, t0, t1, iterations, lm, ep, motion_only, depth_only)
         -> [dx, dz]; poses [N,7] and disps [N,h,w] are updated in place (dz is None with motion_only, as in the reference)
@@ -12,8 +13,19 @@ Poses are (t, q xyzw), world to camera.  Every tensor lives on the GPU; there is
 stream, and ba issues no host synchronisation: the number K of depth frames is eta.shape[0].  If that differs from the number of
 distinct frames in cat([t0, t1), ii), nothing is updated and dx, dz come back as NaN.  The window t1 - t0 is limited to 512 frames.
 
-The correlation kernels of the same extension (altcorr_forward / altcorr_backward, corr_index_forward / corr_index_backward) belong
-to the DROID network and are not provided here.
+The correlation lookups of the update operator (modules/droid_net/corr.py), backed by `sgr_corr_*` (csrc/sgr_corr.hip); rd = 2*radius+1:
+
+    corr_index_forward(volume [B,h1,w1,h2,w2] fp16|fp32, coords [B,2,h1,w1] fp32, radius) -> [corr [B,rd,rd,h1,w1]]
+    corr_index_backward(volume, coords, corr_grad, radius) -> [volume_grad]        (only the shape of volume is used)
+    altcorr_forward(fmap1 [B,H1,W1,C], fmap2 [B,H2,W2,C], coords [B,N,H1,W1,2], radius) -> [corr [B,N,rd*rd,H1,W1]]      (fp32)
+    altcorr_backward(fmap1, fmap2, coords, corr_grad, radius) -> [fmap1_grad, fmap2_grad, coords_grad]                   (fp32)
+
+Outputs run over the x offset first, then the y offset, as in the reference.  A sample is bilinear with zero padding, summed in fp32
+and rounded once.  A pixel whose floor(x0) or floor(y0) is not finite, or lies more than radius+2 outside the map, gives exact zeros
+and takes part in no gradient: no coordinate value reaches memory.  B*h1*w1 (times N for altcorr) and h2*w2 must each fit int32, C is
+a positive multiple of 4, radius <= 1023.  Everything is bitwise reproducible except fmap2_grad, a scatter summed with fp32 atomic
+adds whose last bits depend on arrival order.  What is not provided: half-precision altcorr_* (the reference's caller casts to fp32),
+fp64, a CPU path, and a gradient with respect to coords (coords_grad is all zeros, as in the reference).
 """
 import ctypes as C
 
@@ -21,7 +33,8 @@ import torch
 
 from splat_slam_amd import _native as nat
 
-__all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj"]
+__all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "corr_index_forward", "corr_index_backward", "altcorr_forward",
+           "altcorr_backward"]
 
 
 def _gpu(name, t, dtype, ndim=None):
@@ -177,3 +190,118 @@ def iproj(poses, disps, intrinsics):
         nat.check(nat.lib().sgr_dba_iproj(poses.data_ptr(), disps.data_ptr(), n, h, w, intrinsics.data_ptr(), points.data_ptr(),
                                           _stream(dev)), "sgr_dba_iproj")
     return points
+
+
+# ---- correlation lookups (csrc/sgr_corr.hip)
+_I32 = 2 ** 31 - 1
+
+
+def _radius(fn, radius):
+    radius = int(radius)
+    if radius < 0:
+        raise ValueError(f"droid_backends.{fn}: radius must be >= 0, got {radius}")
+    if radius > nat.SGR_CORR_MAX_RADIUS:
+        raise ValueError(f"droid_backends.{fn}: radius {radius} exceeds the supported {nat.SGR_CORR_MAX_RADIUS}")
+    return radius
+
+
+def _index_args(fn, volume, coords, radius):
+    if not isinstance(volume, torch.Tensor):
+        raise TypeError("droid_backends: volume must be a torch.Tensor")
+    if volume.dtype not in (torch.float16, torch.float32):
+        raise TypeError(f"droid_backends: volume must be torch.float16 or torch.float32, got {volume.dtype}")
+    _gpu("volume", volume, volume.dtype, 5)
+    _gpu("coords", coords, torch.float32, 4)
+    B, h1, w1, h2, w2 = volume.shape
+    if tuple(coords.shape) != (B, 2, h1, w1):
+        raise ValueError(f"droid_backends.{fn}: coords must be [B,2,h1,w1] = {(B, 2, h1, w1)}, got {tuple(coords.shape)}")
+    radius = _radius(fn, radius)
+    if B * h1 * w1 > _I32 or h2 * w2 > _I32:
+        raise ValueError(f"droid_backends.{fn}: B*h1*w1 and h2*w2 must each fit in int32, got volume {tuple(volume.shape)}")
+    return B, h1, w1, h2, w2, radius, nat.SGR_CORR_F16 if volume.dtype == torch.float16 else nat.SGR_CORR_F32
+
+
+def corr_index_forward(volume, coords, radius):
+    B, h1, w1, h2, w2, radius, dtype = _index_args("corr_index_forward", volume, coords, radius)
+    dev = _same_device(volume, coords)
+    rd = 2 * radius + 1
+    corr = torch.empty((B, rd, rd, h1, w1), dtype=volume.dtype, device=dev)
+    if corr.numel() == 0:
+        return [corr]
+    if volume.numel() == 0:         # an empty map: every corner is outside it
+        return [corr.zero_()]
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().sgr_corr_index_forward(volume.data_ptr(), coords.data_ptr(), corr.data_ptr(), dtype, B, h1, w1, h2, w2, radius,
+                                                   _stream(dev)), "sgr_corr_index_forward")
+    return [corr]
+
+
+def corr_index_backward(volume, coords, corr_grad, radius):
+    B, h1, w1, h2, w2, radius, dtype = _index_args("corr_index_backward", volume, coords, radius)
+    _gpu("corr_grad", corr_grad, volume.dtype, 5)
+    rd = 2 * radius + 1
+    if tuple(corr_grad.shape) != (B, rd, rd, h1, w1):
+        raise ValueError(f"droid_backends.corr_index_backward: corr_grad must be [B,rd,rd,h1,w1] = {(B, rd, rd, h1, w1)}, "
+                         f"got {tuple(corr_grad.shape)}")
+    dev = _same_device(volume, coords, corr_grad)
+    volume_grad = torch.empty_like(volume)
+    if volume_grad.numel() == 0:
+        return [volume_grad]
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().sgr_corr_index_backward(coords.data_ptr(), corr_grad.data_ptr(), volume_grad.data_ptr(), dtype, B, h1, w1, h2,
+                                                    w2, radius, _stream(dev)), "sgr_corr_index_backward")
+    return [volume_grad]
+
+
+def _alt_args(fn, fmap1, fmap2, coords, radius):
+    _gpu("fmap1", fmap1, torch.float32, 4)
+    _gpu("fmap2", fmap2, torch.float32, 4)
+    _gpu("coords", coords, torch.float32, 5)
+    B, H1, W1, C = fmap1.shape
+    if fmap2.shape[0] != B or fmap2.shape[3] != C:
+        raise ValueError(f"droid_backends.{fn}: fmap2 must be [B,H2,W2,C] with B = {B}, C = {C}, got {tuple(fmap2.shape)}")
+    H2, W2 = fmap2.shape[1:3]
+    N = coords.shape[1]
+    if tuple(coords.shape) != (B, N, H1, W1, 2):
+        raise ValueError(f"droid_backends.{fn}: coords must be [B,N,H1,W1,2] = {(B, 'N', H1, W1, 2)}, got {tuple(coords.shape)}")
+    if C < 4 or C % 4:
+        raise ValueError(f"droid_backends.{fn}: the channel count must be a positive multiple of 4, got {C}")
+    radius = _radius(fn, radius)
+    if B * N * H1 * W1 > _I32 or H2 * W2 > _I32:
+        raise ValueError(f"droid_backends.{fn}: B*N*H1*W1 and H2*W2 must each fit in int32")
+    return B, N, H1, W1, H2, W2, C, radius
+
+
+def altcorr_forward(fmap1, fmap2, coords, radius):
+    B, N, H1, W1, H2, W2, C, radius = _alt_args("altcorr_forward", fmap1, fmap2, coords, radius)
+    dev = _same_device(fmap1, fmap2, coords)
+    rd = 2 * radius + 1
+    corr = torch.empty((B, N, rd * rd, H1, W1), dtype=torch.float32, device=dev)
+    if corr.numel() == 0:
+        return [corr]
+    if fmap2.numel() == 0:
+        return [corr.zero_()]
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().sgr_corr_alt_forward(fmap1.data_ptr(), fmap2.data_ptr(), coords.data_ptr(), corr.data_ptr(), B, N, H1, W1, H2,
+                                                 W2, C, radius, _stream(dev)), "sgr_corr_alt_forward")
+    return [corr]
+
+
+def altcorr_backward(fmap1, fmap2, coords, corr_grad, radius):
+    B, N, H1, W1, H2, W2, C, radius = _alt_args("altcorr_backward", fmap1, fmap2, coords, radius)
+    _gpu("corr_grad", corr_grad, torch.float32, 5)
+    rd = 2 * radius + 1
+    if tuple(corr_grad.shape) != (B, N, rd * rd, H1, W1):
+        raise ValueError(f"droid_backends.altcorr_backward: corr_grad must be [B,N,rd*rd,H1,W1] = {(B, N, rd * rd, H1, W1)}, "
+                         f"got {tuple(corr_grad.shape)}")
+    dev = _same_device(fmap1, fmap2, coords, corr_grad)
+    fmap2_grad = torch.zeros_like(fmap2)            # the kernel adds into it
+    coords_grad = torch.zeros_like(coords)
+    if corr_grad.numel() == 0 or fmap2.numel() == 0:
+        return [torch.zeros_like(fmap1), fmap2_grad, coords_grad]
+    fmap1_grad = torch.empty_like(fmap1)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().sgr_corr_alt_backward(fmap1.data_ptr(), fmap2.data_ptr(), coords.data_ptr(), corr_grad.data_ptr(),
+                                                  fmap1_grad.data_ptr(), fmap2_grad.data_ptr(), B, N, H1, W1, H2, W2, C, radius,
+                                                  _stream(dev)), "sgr_corr_alt_backward")
+    return [fmap1_grad, fmap2_grad, coords_grad]

@@ -50,6 +50,9 @@
  *   sknn_dist2             -> simple_knn._C.distCUDA2, thirdparty/gaussian_splatting/scene/gaussian_model.py:18,194-200
  *   sgr_dba_*              -> droid_backends.{ba, frame_distance, projmap, iproj, depth_filter} (thirdparty/glorie_slam/lib/droid.cpp),
  *                             thirdparty/glorie_slam/depth_video.py:195-204 (frame_distance), :231 (ba), :363 (depth_filter)
+ *   sgr_corr_*             -> droid_backends.{corr_index_forward, corr_index_backward, altcorr_forward, altcorr_backward}
+ *                             (thirdparty/glorie_slam/lib/droid.cpp), called from CorrSampler and CorrLayer of
+ *                             thirdparty/glorie_slam/modules/droid_net/corr.py:27,34,98,106
  *   se3_*                  -> lietorch SE3 ops used on the mapping path, thirdparty/glorie_slam/depth_video.py:327-330
  *                             (SE3(pose).inv().matrix()), and the tau convention of
  *                             thirdparty/monogs/utils/pose_utils.py:66-98.
@@ -671,6 +674,27 @@ int sgr_dba_iproj(const float* poses, const float* disps, int32_t num_frames, in
 /* counter [num, ht, wd]: neighbours ix-1, ix-2, ix-3, ix+3, ix+4, ix+5 of each ix = inds[b] that agree within thresh[b] */
 int sgr_dba_depth_filter(const float* poses, const float* disps, int32_t num_frames, int32_t ht, int32_t wd, const float* intrinsics,
                          const int64_t* inds, int32_t num, const float* thresh, float* counter, void* stream);
+
+/* Correlation lookups of the tracker's update operator (droid_backends).  rd = 2*radius + 1; outputs run over the x offset first,
+ * then the y offset.  A sample is bilinear with zero padding; a pixel whose floor(x0) or floor(y0) is not finite or lies outside
+ * [-(radius+2), w2+radius+1] resp. [-(radius+2), h2+radius+1] reads nothing and gives zeros (no coordinate value reaches memory).
+ * Sums are kept in fp32 and rounded once; every output element is written exactly once (no zero-fill by the caller), except
+ * fmap2_grad, which must be ZERO on entry and is accumulated with fp32 atomic adds (the only output that is not bitwise
+ * reproducible).  batch*h1*w1 (times num for the alt pair) and h2*w2 must each fit int32 (SGR_ERR_CAPACITY); radius <= 1023.
+ * corr_index: volume, volume_grad [batch,h1,w1,h2,w2] and corr, corr_grad [batch,rd,rd,h1,w1] in `dtype`; coords [batch,2,h1,w1]
+ * fp32 (x, y planes).  corr_alt: fmap1 [batch,h1,w1,channels], fmap2 [batch,h2,w2,channels], coords [batch,num,h1,w1,2] (x, y),
+ * corr, corr_grad [batch,num,rd*rd,h1,w1], all fp32; channels is a positive multiple of 4. */
+#define SGR_CORR_F32 0
+#define SGR_CORR_F16 1
+int sgr_corr_index_forward(const void* volume, const float* coords, void* corr, int32_t dtype, int32_t batch, int32_t h1, int32_t w1,
+                           int32_t h2, int32_t w2, int32_t radius, void* stream);
+int sgr_corr_index_backward(const float* coords, const void* corr_grad, void* volume_grad, int32_t dtype, int32_t batch, int32_t h1,
+                            int32_t w1, int32_t h2, int32_t w2, int32_t radius, void* stream);
+int sgr_corr_alt_forward(const float* fmap1, const float* fmap2, const float* coords, float* corr, int32_t batch, int32_t num, int32_t h1,
+                         int32_t w1, int32_t h2, int32_t w2, int32_t channels, int32_t radius, void* stream);
+int sgr_corr_alt_backward(const float* fmap1, const float* fmap2, const float* coords, const float* corr_grad, float* fmap1_grad,
+                          float* fmap2_grad, int32_t batch, int32_t num, int32_t h1, int32_t w1, int32_t h2, int32_t w2, int32_t channels,
+                          int32_t radius, void* stream);
 
 /* SE3 ops, batched over n.  Pose = (tx,ty,tz,qx,qy,qz,qw) as in lietorch / depth_video.py:69; tau = (rho, theta). */
 int se3_exp(const float* tau, int64_t n, float* pose_out, void* stream);

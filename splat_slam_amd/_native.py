@@ -129,6 +129,8 @@ class SgrDbaProblem(C.Structure):
 
 
 SGR_DBA_MAX_WINDOW = 512
+SGR_CORR_F32, SGR_CORR_F16 = 0, 1
+SGR_CORR_MAX_RADIUS = 1023
 
 
 # name -> (restype, argtypes); must list every symbol include/splat_hip.h declares (tests/test_abi.py checks)
@@ -211,6 +213,10 @@ SIGNATURES = {
     "sgr_dba_projmap": (C.c_int, [_fp, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_int32, _fp, _fp, _fp]),
     "sgr_dba_iproj": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp]),
     "sgr_dba_depth_filter": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, _fp, _fp, _fp]),
+    "sgr_corr_index_forward": (C.c_int, [_fp, _fp, _fp] + [C.c_int32] * 7 + [_fp]),
+    "sgr_corr_index_backward": (C.c_int, [_fp, _fp, _fp] + [C.c_int32] * 7 + [_fp]),
+    "sgr_corr_alt_forward": (C.c_int, [_fp, _fp, _fp, _fp] + [C.c_int32] * 8 + [_fp]),
+    "sgr_corr_alt_backward": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp] + [C.c_int32] * 8 + [_fp]),
     "se3_exp": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_log": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_inv": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
