@@ -50,6 +50,9 @@
  *   sknn_dist2             -> simple_knn._C.distCUDA2, thirdparty/gaussian_splatting/scene/gaussian_model.py:18,194-200
  *   sgr_dba_*              -> droid_backends.{ba, frame_distance, projmap, iproj, depth_filter} (thirdparty/glorie_slam/lib/droid.cpp),
  *                             thirdparty/glorie_slam/depth_video.py:195-204 (frame_distance), :231 (ba), :363 (depth_filter)
+ *   sgr_dspo_*             -> stage 2 ("depth_scale") of DepthVideo.dspo, thirdparty/glorie_slam/depth_video.py:236-299:
+ *                             BA_with_scale_shift (thirdparty/glorie_slam/geom/ba.py) and align_scale_and_shift
+ *                             (src/utils/common.py:68-104)
  *   sgr_corr_*             -> droid_backends.{corr_index_forward, corr_index_backward, altcorr_forward, altcorr_backward}
  *                             (thirdparty/glorie_slam/lib/droid.cpp), called from CorrSampler and CorrLayer of
  *                             thirdparty/glorie_slam/modules/droid_net/corr.py:27,34,98,106
@@ -674,6 +677,47 @@ int sgr_dba_iproj(const float* poses, const float* disps, int32_t num_frames, in
 /* counter [num, ht, wd]: neighbours ix-1, ix-2, ix-3, ix+3, ix+4, ix+5 of each ix = inds[b] that agree within thresh[b] */
 int sgr_dba_depth_filter(const float* poses, const float* disps, int32_t num_frames, int32_t ht, int32_t wd, const float* intrinsics,
                          const int64_t* inds, int32_t num, const float* thresh, float* counter, void* stream);
+
+/* DSPO stage 2 of the tracker ("depth_scale"): disparities, and one scale and shift per frame for the mono-depth prior, with the
+ * poses fixed.  Conventions are those of sgr_dba_*; the algorithm is stated in DESIGN.md section 3, "DSPO stage 2".
+ * sgr_dspo_align: for each of `num` frames of `pixels` pixels, the scale s and shift q that minimise sum w (s prediction + q - target)^2
+ * and the mean error sum w |s prediction + q - target| / sum w, as out [num, 3] = (s, q, error).  Sums, the 2 x 2 solve and the error
+ * are fp64, rounded once; a zero determinant gives what IEEE arithmetic gives (inf / NaN).  weights: NULL with SGR_DSPO_WEIGHTS_NONE
+ * (all ones), float with _F32, bytes (non-zero = 1) with _U8.
+ * sgr_dspo_ba runs `iterations` Gauss-Newton steps in place on the disparities of the M depth frames kx = sorted unique(ii) and on
+ * their scales and shifts, with no host synchronisation.  edge_keep (may be NULL = all) masks edges out; a depth frame none of whose
+ * edges is kept is left untouched and its dwq and dz rows are zero.  dwq is [M, 2] and dz [M, ht*wd] of the last step.  A frame
+ * whose reduced 2 x 2 system is not positive definite gets dwq = 0 (that frame alone).  When M differs from the number of distinct
+ * ii found on the device, nothing is updated and dwq, dz are NaN. */
+#define SGR_DSPO_WEIGHTS_NONE 0
+#define SGR_DSPO_WEIGHTS_F32 1
+#define SGR_DSPO_WEIGHTS_U8 2
+typedef struct SgrDspoProblem {
+  const float* poses;              /* [num_poses, 7], not changed */
+  int32_t num_poses;
+  float* disps;                    /* [num_frames, ht, wd], updated */
+  int32_t num_frames, ht, wd;
+  const float* intrinsics;         /* [4] */
+  const float* mono_disps;         /* [num_frames, ht, wd]: mono-depth prior as disparity, < 1e-6 where there is none */
+  const uint8_t* valid_depth_mask; /* [num_frames, ht, wd]: non-zero where the disparity passed the two-view consistency check */
+  float* scales;                   /* [num_frames], updated */
+  float* shifts;                   /* [num_frames], updated */
+  const float* targets;            /* [num_edges, ht, wd, 2]: (x, y) per pixel */
+  const float* weights;            /* [num_edges, ht, wd, 2] */
+  const float* eta;                /* [num_depth, ht, wd] */
+  const int64_t* ii;               /* [num_edges] */
+  const int64_t* jj;               /* [num_edges] */
+  const uint8_t* edge_keep;        /* [num_edges] or NULL */
+  int32_t num_edges, num_depth;
+  int32_t ignore_frames, iterations;
+  float lm, ep, alpha;
+  float* dwq;                      /* [num_depth, 2] out */
+  float* dz;                       /* [num_depth, ht*wd] out */
+} SgrDspoProblem;
+int sgr_dspo_align(const float* prediction, const float* target, const void* weights, int32_t weights_kind, int32_t num, int32_t pixels,
+                   float* out, void* stream);
+size_t sgr_dspo_scratch_bytes(int32_t num_frames, int32_t num_edges, int32_t num_depth, int32_t ht, int32_t wd);
+int sgr_dspo_ba(const SgrDspoProblem* problem, void* scratch, size_t scratch_bytes, void* stream);
 
 /* Correlation lookups of the tracker's update operator (droid_backends).  rd = 2*radius + 1; outputs run over the x offset first,
  * then the y offset.  A sample is bilinear with zero padding; a pixel whose floor(x0) or floor(y0) is not finite or lies outside

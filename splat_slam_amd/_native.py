@@ -128,7 +128,16 @@ class SgrDbaProblem(C.Structure):
                 ("depth_only", C.c_int32), ("dx", _fp), ("dz", _fp)]
 
 
+class SgrDspoProblem(C.Structure):
+    _fields_ = [("poses", _fp), ("num_poses", C.c_int32), ("disps", _fp), ("num_frames", C.c_int32), ("ht", C.c_int32),
+                ("wd", C.c_int32), ("intrinsics", _fp), ("mono_disps", _fp), ("valid_depth_mask", _fp), ("scales", _fp),
+                ("shifts", _fp), ("targets", _fp), ("weights", _fp), ("eta", _fp), ("ii", _fp), ("jj", _fp), ("edge_keep", _fp),
+                ("num_edges", C.c_int32), ("num_depth", C.c_int32), ("ignore_frames", C.c_int32), ("iterations", C.c_int32),
+                ("lm", C.c_float), ("ep", C.c_float), ("alpha", C.c_float), ("dwq", _fp), ("dz", _fp)]
+
+
 SGR_DBA_MAX_WINDOW = 512
+SGR_DSPO_WEIGHTS_NONE, SGR_DSPO_WEIGHTS_F32, SGR_DSPO_WEIGHTS_U8 = 0, 1, 2
 SGR_CORR_F32, SGR_CORR_F16 = 0, 1
 SGR_CORR_MAX_RADIUS = 1023
 
@@ -213,6 +222,9 @@ SIGNATURES = {
     "sgr_dba_projmap": (C.c_int, [_fp, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_int32, _fp, _fp, _fp]),
     "sgr_dba_iproj": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp]),
     "sgr_dba_depth_filter": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, _fp, _fp, _fp]),
+    "sgr_dspo_align": (C.c_int, [_fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]),
+    "sgr_dspo_scratch_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "sgr_dspo_ba": (C.c_int, [C.POINTER(SgrDspoProblem), _fp, C.c_size_t, _fp]),
     "sgr_corr_index_forward": (C.c_int, [_fp, _fp, _fp] + [C.c_int32] * 7 + [_fp]),
     "sgr_corr_index_backward": (C.c_int, [_fp, _fp, _fp] + [C.c_int32] * 7 + [_fp]),
     "sgr_corr_alt_forward": (C.c_int, [_fp, _fp, _fp, _fp] + [C.c_int32] * 8 + [_fp]),
