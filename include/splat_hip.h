@@ -50,6 +50,7 @@
  *   sknn_dist2             -> simple_knn._C.distCUDA2, thirdparty/gaussian_splatting/scene/gaussian_model.py:18,194-200
  *   sgr_dba_*              -> droid_backends.{ba, frame_distance, projmap, iproj, depth_filter} (thirdparty/glorie_slam/lib/droid.cpp),
  *                             thirdparty/glorie_slam/depth_video.py:195-204 (frame_distance), :231 (ba), :363 (depth_filter)
+ *   sgr_video_*            -> DepthVideo.upsample (:154-158) and update_valid_depth_mask (:340-375) of the same file
  *   sgr_dspo_*             -> stage 2 ("depth_scale") of DepthVideo.dspo, thirdparty/glorie_slam/depth_video.py:236-299:
  *                             BA_with_scale_shift (thirdparty/glorie_slam/geom/ba.py) and align_scale_and_shift
  *                             (src/utils/common.py:68-104)
@@ -718,6 +719,33 @@ int sgr_dspo_align(const float* prediction, const float* target, const void* wei
                    float* out, void* stream);
 size_t sgr_dspo_scratch_bytes(int32_t num_frames, int32_t num_edges, int32_t num_depth, int32_t ht, int32_t wd);
 int sgr_dspo_ba(const SgrDspoProblem* problem, void* scratch, size_t scratch_bytes, void* stream);
+
+/* The keyframe store of the tracker (DepthVideo, thirdparty/glorie_slam/depth_video.py): convex upsampling of the disparity maps
+ * (:154-158) and the two-view consistency mask (update_valid_depth_mask, :340-375).  Stated in DESIGN.md section 3, "Depth video".
+ * inds [num] int64 are distinct frame indices; an index outside [0, num_frames) makes its slot a no-op (its thresh is NaN).
+ * num <= 65535.  Everything is stream-ordered, allocates nothing and is bitwise reproducible.
+ * sgr_video_cvx_upsample: disps [num_frames, ht, wd], mask [num, 576, ht, wd] of logits (fp32 or fp16), channel k*64 + dy*8 + dx with
+ * k = 3*(ny+1) + (nx+1); disps_up [num_frames, 8*ht, 8*wd] (16-byte aligned), of which only the frames named in inds are written:
+ * out[8y+dy, 8x+dx] = sum_k softmax_k(mask[k*64+dy*8+dx, y, x]) * d[y+ny, x+nx], d = 0 outside the map, the softmax in fp32.
+ * sgr_video_depth_thresh: thresh[b] = rel * mean(1.0f / disp) over frame inds[b]; the sum is fp64, rounded once.
+ * sgr_video_mask_from_counts: counts [num, ht, wd] as sgr_dba_depth_filter writes them; candidates are the pixels with
+ * counts >= visible_num whose depth 1.0f / disp is not NaN; mask_out [num_frames, ht, wd] bytes (only the frames of inds) =
+ * candidate && depth < 3.0f * (lower median of the candidates' depths), all zero when there is no candidate.
+ * sgr_video_valid_mask: the chain thresholds -> sgr_dba_depth_filter -> mask; poses cover num_frames.
+ * scratch: sgr_video_scratch_bytes(num, ht, wd) bytes, 16-byte aligned (0 = unsupported sizes). */
+#define SGR_VIDEO_MASK_F32 0
+#define SGR_VIDEO_MASK_F16 1
+int sgr_video_cvx_upsample(const float* disps, int32_t num_frames, int32_t ht, int32_t wd, const int64_t* inds, int32_t num,
+                           const void* mask, int32_t mask_kind, float* disps_up, void* stream);
+int sgr_video_depth_thresh(const float* disps, int32_t num_frames, int32_t ht, int32_t wd, const int64_t* inds, int32_t num, float rel,
+                           float* thresh, void* stream);
+size_t sgr_video_scratch_bytes(int32_t num, int32_t ht, int32_t wd);
+int sgr_video_mask_from_counts(const float* disps, int32_t num_frames, int32_t ht, int32_t wd, const int64_t* inds, int32_t num,
+                               const float* counts, int32_t visible_num, uint8_t* mask_out, void* scratch, size_t scratch_bytes,
+                               void* stream);
+int sgr_video_valid_mask(const float* poses, const float* disps, int32_t num_frames, int32_t ht, int32_t wd, const float* intrinsics,
+                         const int64_t* inds, int32_t num, float rel, int32_t visible_num, uint8_t* mask_out, void* scratch,
+                         size_t scratch_bytes, void* stream);
 
 /* Correlation lookups of the tracker's update operator (droid_backends).  rd = 2*radius + 1; outputs run over the x offset first,
  * then the y offset.  A sample is bilinear with zero padding; a pixel whose floor(x0) or floor(y0) is not finite or lies outside

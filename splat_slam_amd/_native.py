@@ -139,6 +139,8 @@ class SgrDspoProblem(C.Structure):
 SGR_DBA_MAX_WINDOW = 512
 SGR_DSPO_WEIGHTS_NONE, SGR_DSPO_WEIGHTS_F32, SGR_DSPO_WEIGHTS_U8 = 0, 1, 2
 SGR_CORR_F32, SGR_CORR_F16 = 0, 1
+SGR_VIDEO_MASK_F32, SGR_VIDEO_MASK_F16 = 0, 1
+SGR_VIDEO_MAX_FRAMES = 65535
 SGR_CORR_MAX_RADIUS = 1023
 
 
@@ -225,6 +227,13 @@ SIGNATURES = {
     "sgr_dspo_align": (C.c_int, [_fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]),
     "sgr_dspo_scratch_bytes": (C.c_size_t, [C.c_int32] * 5),
     "sgr_dspo_ba": (C.c_int, [C.POINTER(SgrDspoProblem), _fp, C.c_size_t, _fp]),
+    "sgr_video_cvx_upsample": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, _fp, C.c_int32, _fp, _fp]),
+    "sgr_video_depth_thresh": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, C.c_float, _fp, _fp]),
+    "sgr_video_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "sgr_video_mask_from_counts": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, _fp, C.c_int32, _fp, _fp, C.c_size_t,
+                                             _fp]),
+    "sgr_video_valid_mask": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, C.c_float, C.c_int32, _fp, _fp,
+                                       C.c_size_t, _fp]),
     "sgr_corr_index_forward": (C.c_int, [_fp, _fp, _fp] + [C.c_int32] * 7 + [_fp]),
     "sgr_corr_index_backward": (C.c_int, [_fp, _fp, _fp] + [C.c_int32] * 7 + [_fp]),
     "sgr_corr_alt_forward": (C.c_int, [_fp, _fp, _fp, _fp] + [C.c_int32] * 8 + [_fp]),

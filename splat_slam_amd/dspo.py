@@ -19,8 +19,8 @@ and nothing synchronises with the host: M is eta.shape[0]; if it differs from th
 come back as NaN.  Differences from the reference, all deliberate: a frame whose reduced 2 x 2 system is not positive definite gets a
 zero step on its own (the reference factors every frame as one matrix and zeroes them all); edges are masked (edge_keep) instead of
 removed on the host; depth_scale_step clamps the disparities of the frames it moved (the reference clamps the whole buffer, whose other
-frames stage 1 has clamped already).  What is not provided: a batch dimension, update_valid_depth_mask (the two-view consistency mask
-stays with the caller), the Python dense BA and MoBA of geom/ba.py.
+frames stage 1 has clamped already).  What is not provided: a batch dimension, the Python dense BA and MoBA of geom/ba.py.  The two-view
+consistency mask (update_valid_depth_mask) and the class around all of this are splat_slam_amd.depth_video.
 """
 import ctypes as C
 
