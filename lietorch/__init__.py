@@ -3,7 +3,12 @@
 operations the reference's tracker glue uses, backed by the gfx950 `se3_*` entry points of
 include/splat_hip.h.  Pose layout (tx,ty,tz,qx,qy,qz,qw); tangent (rho, theta) -- the same order as
 /root/reference/thirdparty/monogs/utils/pose_utils.py:81-98.  Forward only (the mapping path never differentiates it).
-GPU tensors only: there is no CPU path.
+GPU tensors only: there is no CPU path.  Everything is computed and returned in fp32: an input of another floating dtype (fp64,
+fp16) is rounded to fp32 on the way in and the result is NOT cast back.  Batch shapes broadcast (`[1,7] * [N,7]`, a pose `[N,1,7]`
+on points `[N,P,3]`); views are made contiguous first.  Accuracy: tests/se3_ref.py derives, and tests/test_gpu_se3.py holds, a per-element bound C_op * 2^-24 * M at every angle (small-angle
+`exp` / `log` included): C_op <= 28 roundings, M = the terms that are summed plus, for `exp` and `log`, what the rounded angle moves
+them by.  Against the plain sum of terms that is more than 32 roundings where an op is ill conditioned in its angle (`log` rho: up to
+53; `exp` around pi and 2 pi); DESIGN.md section 3 has the figures.
 """
 import torch
 

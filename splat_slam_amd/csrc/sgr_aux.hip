@@ -718,16 +718,22 @@ __global__ void __launch_bounds__(256) se3_kernel(int64_t n, const float* __rest
     float rho[3] = {tau[0], tau[1], tau[2]}, th[3] = {tau[3], tau[4], tau[5]};
     float t2 = th[0] * th[0] + th[1] * th[1] + th[2] * th[2];
     float ang = sqrtf(t2);
-    float A, Bc, Cc, imag, real;   // sin(a)/a, (1-cos a)/a^2, (a - sin a)/a^3, sin(a/2)/a, cos(a/2)
+    float Bc, Cc, imag, real;   // (1-cos a)/a^2, (a - sin a)/a^3, sin(a/2)/a, cos(a/2)
+    // Neither coefficient is formed by a difference of nearly equal numbers: 1 - cosf(a) is 0 up to a = 3.4e-4 and keeps a few
+    // bits up to 3e-2, a - sinf(a) likewise (the translation was off by up to 1000 ulp of |rho| for a in [1e-4, 1e-2]).
     if (ang < 1e-4f) {
-      A = 1.f - t2 / 6.f; Bc = 0.5f - t2 / 24.f; Cc = 1.f / 6.f - t2 / 120.f;
-      imag = 0.5f - t2 / 48.f; real = 1.f - t2 / 8.f;
+      Bc = 0.5f - t2 / 24.f; imag = 0.5f - t2 / 48.f; real = 1.f - t2 / 8.f;
     } else {
-      float s = sinf(ang), c = cosf(ang);
-      A = s / ang; Bc = (1.f - c) / t2; Cc = (ang - s) / (t2 * ang);
-      imag = sinf(0.5f * ang) / ang; real = cosf(0.5f * ang);
+      float h = 0.5f * ang, sh = sinf(h), r = sh / h;
+      Bc = 0.5f * r * r;                                     // 2 sin^2(a/2) / a^2
+      imag = sh / ang; real = cosf(h);
     }
-    (void)A;
+    // C: Taylor series below a = 1 (five terms: the first one left out is a^10 / 13! <= 1.6e-10, 0.02 ulp of C >= 0.158); from 1 on
+    // the difference loses 2 sin a / (a - sin a) <= 10.7 roundings, within the bound the tests hold the translation to (se3_ref.py)
+    if (ang < 1.f)
+      Cc = 1.66666667e-01f + t2 * (-8.33333333e-03f + t2 * (1.98412698e-04f + t2 * (-2.75573192e-06f + t2 * 2.50521084e-08f)));
+    else
+      Cc = (ang - sinf(ang)) / (t2 * ang);
     // t = V rho,  V = I + B [th]x + C [th]x^2
     float c1[3] = {th[1] * rho[2] - th[2] * rho[1], th[2] * rho[0] - th[0] * rho[2], th[0] * rho[1] - th[1] * rho[0]};
     float c2[3] = {th[1] * c1[2] - th[2] * c1[1], th[2] * c1[0] - th[0] * c1[2], th[0] * c1[1] - th[1] * c1[0]};
@@ -750,8 +756,12 @@ __global__ void __launch_bounds__(256) se3_kernel(int64_t n, const float* __rest
     float th[3] = {k * p.q[0], k * p.q[1], k * p.q[2]};
     float t2 = th[0] * th[0] + th[1] * th[1] + th[2] * th[2], ang = sqrtf(t2);
     // rho = V^-1 t,  V^-1 = I - 1/2 [th]x + D [th]x^2,  D = (1 - (a/2) cot(a/2)) / a^2
+    // Series sum |B_2n| a^(2n-2) / (2n)! below a = 2 (eight terms: the rest is 0.12 ulp of D there; it converges up to 2 pi), because
+    // 1 - h cot h loses h cot h / (1 - h cot h) of the seven roundings of h cosf(h) / sinf(h): 12 / a^2 at small a, 1.8 at a = 2
     float D;
-    if (ang < 1e-4f) D = 1.f / 12.f + t2 / 720.f;
+    if (ang < 2.f)
+      D = 8.33333333e-02f + t2 * (1.38888889e-03f + t2 * (3.30687831e-05f + t2 * (8.26719577e-07f + t2 * (2.08767570e-08f +
+          t2 * (5.28419014e-10f + t2 * (1.33825365e-11f + t2 * 3.38968030e-13f))))));
     else { float h = 0.5f * ang; D = (1.f - h * cosf(h) / sinf(h)) / t2; }
     float c1[3] = {th[1] * p.t[2] - th[2] * p.t[1], th[2] * p.t[0] - th[0] * p.t[2], th[0] * p.t[1] - th[1] * p.t[0]};
     float c2[3] = {th[1] * c1[2] - th[2] * c1[1], th[2] * c1[0] - th[0] * c1[2], th[0] * c1[1] - th[1] * c1[0]};
@@ -800,7 +810,8 @@ __global__ void __launch_bounds__(256) se3_kernel(int64_t n, const float* __rest
 
 template <int OP>
 static int se3_launch(int64_t n, const float* a, const float* b, float* out, void* stream) {
-  if (n < 0 || (n > 0 && (!a || !out))) return set_error(SGR_ERR_INVALID, "se3: null argument");
+  constexpr bool binary = OP == OP_MUL || OP == OP_ACT || OP == OP_ADJT;
+  if (n < 0 || (n > 0 && (!a || !out || (binary && !b)))) return set_error(SGR_ERR_INVALID, "se3: null argument");
   if (n == 0) return SGR_OK;
   hipLaunchKernelGGL(se3_kernel<OP>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, a, b, out);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "se3 launch failed");
