@@ -694,9 +694,14 @@ __global__ void __launch_bounds__(kThreads) dz_kernel(int P, int T, const int* _
     for (int n = 0; n < 6; ++n) dw += F[(size_t)n * P + p] * dx[6 * a + n];
     s += dw;
   }
-  const float d = Q[ko] * (W[ko] - s);
-  dz[ko] = d;
-  disps[(size_t)kx[k] * P + p] += d;
+  // the step is rounded once, and that rounded step is what moves the disparity: contracted into an FMA the map would move by the
+  // unrounded product and disps_after != disps_before + dz in the last bit
+  {
+#pragma clang fp contract(off)
+    const float d = Q[ko] * (W[ko] - s);
+    dz[ko] = d;
+    disps[(size_t)kx[k] * P + p] += d;
+  }
 }
 
 // ================================================================================================================================

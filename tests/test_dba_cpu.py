@@ -159,3 +159,103 @@ def test_package_exports_the_reference_names_and_documents_what_it_leaves_out():
     for name in ("ba", "frame_distance", "projmap", "depth_filter", "iproj"):
         assert callable(getattr(db, name))
     assert "altcorr" in db.__doc__ and "corr_index" in db.__doc__ and "not provided" in db.__doc__
+
+
+# ---- the oracle with magnitudes and the three criteria of tests/dba_cases.py, proved on the CPU
+import dba_cases as DC      # noqa: E402
+
+MUTATIONS = {                                   # planted fault -> the smallest case that can show it
+    "drop_last_pixel": "pix:3,5,pose_depth",    # the last pixel of a frame left out of one edge's pose sums
+    "dup_skip_E": "dup",                        # the second of two duplicate edges left out of the merged Eij rows
+    "dup_skip_C": "dup",                        # ... left out of C and w
+    "swap_Hij": "pix:3,5,motion_only",          # Hij and Hji swapped
+    "dz_missing_edge": "pix:3,5,pose_depth",    # one outgoing edge missing from one depth row's dz sum
+    "no_t0_skip": "pix:3,5,pose_depth",         # the back-substitution does not skip t0
+    "clamp_oob": "oob",                         # an out-of-range jj clamped into range instead of dropping the edge
+    "chol_skip_tile": "chol:11,motion_only",    # n = 66: the one trailing 64x64 tile update of the factorisation skipped
+}
+
+
+@pytest.fixture(scope="module")
+def float32_runs():
+    return {name: DC.criteria(name, *DC.emulate(name)) for name in DC.CASES}
+
+
+def test_every_case_keeps_its_decisions_away_from_fp32_rounding():
+    for name in DC.CASES:
+        DC.check_scene(name, want_behind=not name.startswith(("chol", "big")))
+
+
+def test_float32_restatement_is_inside_every_criterion_at_every_case(float32_runs):
+    worst = {}
+    for name, (ratios, broken) in float32_runs.items():
+        assert not broken, (name, broken)
+        for k, r in ratios.items():
+            assert r <= 1.0, (name, k, r)
+            if r > worst.get(k, (0.0, ""))[0]:
+                worst[k] = (r, name)
+    print("\nlargest err / bound of the float32 restatement (an emulation, not the device):")
+    for k in sorted(worst):
+        print(f"  criterion {k}: {worst[k][0]:.3f} at {worst[k][1]}")
+    assert set(worst) == {"A", "B", "C"}
+    singular = float32_runs["win:no_edge_singular"][0]
+    assert "A" not in singular                       # held to dx == 0 instead
+
+
+def test_the_derived_units_are_the_documented_ones():
+    """the per-addend counts DESIGN.md section 3 tabulates are what the formulas give (they do not depend on the case)"""
+    u = DC.oracle("pix:7,9,pose_depth")["units"]
+    P = 63
+    got = dict(Hs=u["Hs"] - 2 * P, vs=u["vs"] - 2 * P, E=u["E"], Cii=u["Cii"], bz=u["bz"])
+    print("\nper-addend units:", got, "C", u["C"], "w", u["w"], "Q", u["Q"], "F", u["F"], "S", u["S"], "Sg", u["Sg"])
+    assert got == DC.DOCUMENTED_UNITS, got
+
+
+@pytest.mark.parametrize("mutation", list(MUTATIONS))
+def test_planted_fault_fails_a_criterion(mutation):
+    name = MUTATIONS[mutation]
+    ratios, broken = DC.criteria(name, *DC.emulate(name, mutate=mutation))
+    print(mutation, name, ratios, broken)
+    assert not DC.passes(ratios, broken)
+    ratios, broken = DC.criteria(name, *DC.emulate(name))        # ... and it is the fault, not the case, that fails
+    assert DC.passes(ratios, broken)
+
+
+def test_blocked_cholesky_restatement_factors_what_numpy_factors():
+    o = DC.oracle("chol:22,motion_only")
+    L = R.blocked_cholesky(o["H"])
+    np.testing.assert_allclose(L, np.linalg.cholesky(o["H"]), rtol=1e-12, atol=1e-12 * np.abs(o["H"]).max() ** 0.5)
+
+
+def test_oracle_solves_its_own_system_to_fp64():
+    o = DC.oracle("pix:7,9,pose_depth")
+    x = R.solve(o).reshape(-1)
+    assert np.all(np.abs(o["H"] @ x - o["g"]) <= R.fp64_solve_term(o, x) + R.bound64(o["H_addends"], o["H_mag"]) @ np.abs(x))
+
+
+def test_oracle_C_w_F_reproduce_the_dz_of_ba():
+    for name in ("pix:7,9,pose_depth", "dup", "oob", "win:both_outside"):
+        c, o = DC.case(name), DC.oracle(name)
+        _, _, dx, dz = R.ba(c["poses"], c["disps"], c["intr"], c["sens"], c["tgt"], c["wgt"], c["eta"], c["ii"], c["jj"], c["t0"], c["t1"], 1,
+                            float(np.float32(c["lm"])), float(np.float32(c["ep"])))
+        np.testing.assert_allclose(R.solve(o), dx, rtol=1e-9, atol=1e-12)
+        mine = R.back_substitute(o, dx).v
+        np.testing.assert_allclose(mine, dz, rtol=1e-9, atol=1e-9 * np.abs(dz).max())
+
+
+def test_splitting_an_edge_into_two_half_weight_copies_changes_nothing():
+    c = DC.case("pix:7,9,pose_depth")
+    a = list(DC.lin_args(c))
+    e = 2                                                          # 3 -> 4, inside the window
+    b = list(a)
+    half = c["wgt"].copy()
+    half[e] *= 0.5
+    b[4] = np.concatenate([c["tgt"], c["tgt"][e:e + 1]])
+    b[5] = np.concatenate([half, half[e:e + 1]])
+    b[7], b[8] = c["ii"] + [c["ii"][e]], c["jj"] + [c["jj"][e]]
+    o1, o2 = R.linearize(*a), R.linearize(*b)
+    scale = np.abs(o1["H_mag"]).max()
+    np.testing.assert_allclose(o2["H"], o1["H"], rtol=0, atol=1e-13 * scale)
+    np.testing.assert_allclose(o2["g"], o1["g"], rtol=0, atol=1e-13 * np.abs(o1["g_mag"]).max())
+    np.testing.assert_allclose(o2["C"].v, o1["C"].v, rtol=1e-13)
+    np.testing.assert_allclose(R.back_substitute(o2, R.solve(o2)).v, R.back_substitute(o1, R.solve(o1)).v, rtol=1e-9, atol=1e-12)
