@@ -57,6 +57,8 @@
  *   sgr_corr_*             -> droid_backends.{corr_index_forward, corr_index_backward, altcorr_forward, altcorr_backward}
  *                             (thirdparty/glorie_slam/lib/droid.cpp), called from CorrSampler and CorrLayer of
  *                             thirdparty/glorie_slam/modules/droid_net/corr.py:27,34,98,106
+ *   sgr_graph_*            -> FactorGraph.update's reprojection and motion features and the edge selection of
+ *                             add_proximity_factors / add_backend_proximity_factors, thirdparty/glorie_slam/factor_graph.py
  *   se3_*                  -> lietorch SE3 ops used on the mapping path, thirdparty/glorie_slam/depth_video.py:327-330
  *                             (SE3(pose).inv().matrix()), and the tau convention of
  *                             thirdparty/monogs/utils/pose_utils.py:66-98.
@@ -767,6 +769,32 @@ int sgr_corr_alt_forward(const float* fmap1, const float* fmap2, const float* co
 int sgr_corr_alt_backward(const float* fmap1, const float* fmap2, const float* coords, const float* corr_grad, float* fmap1_grad,
                           float* fmap2_grad, int32_t batch, int32_t num, int32_t h1, int32_t w1, int32_t h2, int32_t w2, int32_t channels,
                           int32_t radius, void* stream);
+
+/* The factor graph of the tracker (FactorGraph, thirdparty/glorie_slam/factor_graph.py).  Stated in DESIGN.md section 3, "Factor
+ * graph".  Everything is stream-ordered, allocates nothing, synchronises nothing and is bitwise reproducible.
+ * sgr_graph_reproject: projective_transform (geom/projective_ops.py:110-139) with PER-FRAME intrinsics [num_frames,4] (fx, fy, cx, cy)
+ * and, when target [E,ht,wd,2] is given, the motion features of FactorGraph.update.  For edge e = (i, j) and pixel (x, y) with
+ * disparity d of frame i: X0 = ((x-cx_i)/fx_i, (y-cy_i)/fy_i, 1, d), G = G_j G_i^-1 (i == j: t = (-0.1, 0, 0), q = identity),
+ * X1 = R X0.xyz + t d, Z = X1.z < 0.1 ? 1 : X1.z, coords [E,ht,wd,2] = (fx_j X1.x/Z + cx_j, fy_j X1.y/Z + cy_j), valid [E,ht,wd,1] =
+ * X1.z > 0.2, motn [E,4,ht,wd] = clamp((coords - (x, y), target - coords), -64, 64).  target and motn are both given or both NULL.
+ * An edge with an index outside [0, min(num_poses, num_frames)) gets zeros in every output and reads nothing.  E <= 65535.
+ * sgr_graph_select_proximity / _backend: the greedy edge selection of add_proximity_factors (:337-397) and
+ * add_backend_proximity_factors (:400-477) over the distance matrix d (read only), rows i - t0 (t_start_loop), columns j - t1
+ * (t_start), both ending at frame t (t_end); at most 512 x 512.  Entries are visited in ascending distance, equal distances in
+ * ascending flat index.  es [cap,2] int64 receives the pairs in the order of the sequential rule, counts[0] their number and
+ * counts[1] the number of loop pairs among them (loop != 0); nothing is written past cap.  ii_old, jj_old [num_old]: the existing
+ * edges, of any value.  thresh is finite, 0 <= nms <= 512, 0 <= rad.
+ * scratch: sgr_graph_select_scratch_bytes(rows, cols) bytes, 16-byte aligned (0 = unsupported sizes). */
+int sgr_graph_reproject(const float* poses, int32_t num_poses, const float* disps, int32_t num_frames, int32_t ht, int32_t wd,
+                        const float* intrinsics, const int64_t* ii, const int64_t* jj, int32_t num_edges, const float* target,
+                        float* coords, float* valid, float* motn, void* stream);
+size_t sgr_graph_select_scratch_bytes(int32_t rows, int32_t cols);
+int sgr_graph_select_proximity(const float* d, int32_t t0, int32_t t1, int32_t t, const int64_t* ii_old, const int64_t* jj_old,
+                               int32_t num_old, int32_t rad, int32_t nms, float thresh, int32_t max_factors, int64_t* es, int32_t cap,
+                               int32_t* counts, void* scratch, size_t scratch_bytes, void* stream);
+int sgr_graph_select_backend(const float* d, int32_t t_start, int32_t t_end, int32_t t_start_loop, int32_t loop, int32_t nms,
+                             int32_t radius, float thresh, int32_t max_factors, int64_t* es, int32_t cap, int32_t* counts,
+                             void* scratch, size_t scratch_bytes, void* stream);
 
 /* SE3 ops, batched over n.  Pose = (tx,ty,tz,qx,qy,qz,qw) as in lietorch / depth_video.py:69; tau = (rho, theta). */
 int se3_exp(const float* tau, int64_t n, float* pose_out, void* stream);

@@ -142,6 +142,8 @@ SGR_CORR_F32, SGR_CORR_F16 = 0, 1
 SGR_VIDEO_MASK_F32, SGR_VIDEO_MASK_F16 = 0, 1
 SGR_VIDEO_MAX_FRAMES = 65535
 SGR_CORR_MAX_RADIUS = 1023
+SGR_GRAPH_MAX_EDGES = 65535
+SGR_GRAPH_MAX_SIDE = 512
 
 
 # name -> (restype, argtypes); must list every symbol include/splat_hip.h declares (tests/test_abi.py checks)
@@ -238,6 +240,12 @@ SIGNATURES = {
     "sgr_corr_index_backward": (C.c_int, [_fp, _fp, _fp] + [C.c_int32] * 7 + [_fp]),
     "sgr_corr_alt_forward": (C.c_int, [_fp, _fp, _fp, _fp] + [C.c_int32] * 8 + [_fp]),
     "sgr_corr_alt_backward": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp] + [C.c_int32] * 8 + [_fp]),
+    "sgr_graph_reproject": (C.c_int, [_fp, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_int32, _fp, _fp, _fp, _fp,
+                                      _fp]),
+    "sgr_graph_select_scratch_bytes": (C.c_size_t, [C.c_int32] * 2),
+    "sgr_graph_select_proximity": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                             C.c_int32, _fp, C.c_int32, _fp, _fp, C.c_size_t, _fp]),
+    "sgr_graph_select_backend": (C.c_int, [_fp] + [C.c_int32] * 6 + [C.c_float, C.c_int32, _fp, C.c_int32, _fp, _fp, C.c_size_t, _fp]),
     "se3_exp": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_log": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_inv": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
