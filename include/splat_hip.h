@@ -796,6 +796,92 @@ int sgr_graph_select_backend(const float* d, int32_t t_start, int32_t t_end, int
                              int32_t radius, float thresh, int32_t max_factors, int64_t* es, int32_t cap, int32_t* counts,
                              void* scratch, size_t scratch_bytes, void* stream);
 
+/* The update operator of the tracker (UpdateModule, thirdparty/glorie_slam/modules/droid_net/droid_net.py:83-153), inference only.
+ * Stated in DESIGN.md section 3, "Update operator".  Everything is stream-ordered, allocates nothing, synchronises nothing and is
+ * bitwise reproducible.  Activations are channels-last fp16: [pixel m = (edge, y, x)][channel], a row stride counted in halfs that is
+ * a multiple of 8, a 16-byte aligned base.  E*h*w must fit int32.
+ * sgr_update_pack: src [E,C,h,w] with element strides (a NULL data pointer stands for zeros) -> dst[m * dst_stride + c], c < c_pad,
+ * the channels C <= c < c_pad zero; c_pad is a multiple of 8.
+ * sgr_update_conv: out[m][n] = act(bias[n] + eadd[edge][n] + sum_{tap,c} W[n][tap][c] x[m + tap][c]), zero padding, stride 1, square
+ * kernels of size 1, 3 or 7.  Input channel c < split comes from src0[c], the others from src1[c - split] (src1 NULL: all from src0); cin
+ * is the padded channel count, a multiple of 8.  weight is fp16 [round_up(cout, 64)][round_up(ksize^2 * cin, 32)], k = tap * cin + c,
+ * padding zero; bias fp32 [round_up(cout, 64)].  fp16 products, fp32 sums (mfma_f32_16x16x32_f16).  Epilogues on the fp32 sum v:
+ * NONE, RELU, SIGMOID, TANH; ETA = 0.01 softplus(v); GATE = sigmoid(v) * aux0[m][n]; ZR (cout = 256): n < 128 writes sigmoid(v) to
+ * out[m][n], n >= 128 writes sigmoid(v) * aux0[m][n-128] to out2[m][n-128]; BLEND: (1 - z) * aux0 + z * tanh(v) with z = aux1[m][n],
+ * written to out and, as NCHW fp16, to out2.  aux0, aux1 and out2 of ZR are channels-last fp16.
+ * sgr_update_forward: the whole operator.  layer[] order: corr_encoder.0, .2, flow_encoder.0, .2, gru.w, gru.convz|convr (rows
+ * stacked), gru.convq, delta.0|weight.0 (rows stacked), delta.2, weight.2, agg.conv1, agg.conv2, agg.eta.0, agg.upmask.0; input channels
+ * of corr_encoder.0 padded to 200, of flow_encoder.0 to 8.  glo_weight fp32 [384][128], glo_bias [384]: convz_glo, convr_glo,
+ * convq_glo stacked.  K = 0 (ix, eta, upmask unused) skips GraphAgg; otherwise ix[e] in [0, K) is the group of edge e.  Only the
+ * launches first_launch <= i <= last_launch of the 17 are enqueued (0 and 16 for all of them): a single one can be timed on the buffers
+ * that a whole call has left in scratch.
+ * scratch: sgr_update_scratch_bytes(E, K, h, w) bytes, 16-byte aligned (0 = unsupported sizes). */
+#define SGR_UPDATE_F32 0
+#define SGR_UPDATE_F16 1
+#define SGR_UPDATE_ACT_NONE 0
+#define SGR_UPDATE_ACT_RELU 1
+#define SGR_UPDATE_ACT_SIGMOID 2
+#define SGR_UPDATE_ACT_TANH 3
+#define SGR_UPDATE_ACT_ETA 4
+#define SGR_UPDATE_ACT_GATE 5
+#define SGR_UPDATE_ACT_ZR 6
+#define SGR_UPDATE_ACT_BLEND 7
+#define SGR_UPDATE_OUT_CL_F16 0
+#define SGR_UPDATE_OUT_CL_F32 1
+#define SGR_UPDATE_OUT_NCHW_F16 2
+#define SGR_UPDATE_OUT_NCHW_F32 3
+#define SGR_UPDATE_LAYERS 14
+#define SGR_UPDATE_LAUNCHES 17
+typedef struct SgrUpdateTensor {
+  const void* data;
+  int64_t stride[4];               /* elements: edge, channel, y, x */
+  int32_t dtype;                   /* SGR_UPDATE_F32 / _F16 */
+} SgrUpdateTensor;
+typedef struct SgrUpdateConv {
+  const void* src0;
+  const void* src1;
+  int32_t stride0, stride1, split, cin, ksize;
+  int32_t E, h, w;
+  const void* weight;
+  int64_t weight_elems;
+  const float* bias;
+  int32_t cout, act;
+  const float* eadd;               /* [E][eadd_stride] or NULL */
+  int32_t eadd_stride;
+  const void* aux0;
+  const void* aux1;
+  int32_t aux0_stride, aux1_stride;
+  void* out;
+  void* out2;
+  int32_t out_kind, out_stride, out2_stride;
+} SgrUpdateConv;
+typedef struct SgrUpdateLayer {
+  const void* weight;
+  int64_t weight_elems;
+  const float* bias;
+} SgrUpdateLayer;
+typedef struct SgrUpdateWeights {
+  SgrUpdateLayer layer[SGR_UPDATE_LAYERS];
+  const float* glo_weight;
+  const float* glo_bias;
+} SgrUpdateWeights;
+typedef struct SgrUpdateCall {
+  SgrUpdateTensor net, inp, corr, flow;   /* [E,128,h,w], [E,128,h,w], [E,196,h,w], [E,4,h,w] (flow.data NULL: zeros) */
+  int32_t E, h, w, K;
+  const int64_t* ix;               /* [E] */
+  void* net_out;                   /* [E,128,h,w] fp16 */
+  void* delta;                     /* [E,h,w,2] fp16 */
+  void* weight;                    /* [E,h,w,2] fp16 */
+  float* eta;                      /* [K,h,w] */
+  void* upmask;                    /* [K,576,h,w] fp16 */
+  int32_t first_launch, last_launch;
+} SgrUpdateCall;
+size_t sgr_update_scratch_bytes(int32_t E, int32_t K, int32_t h, int32_t w);
+int sgr_update_pack(const SgrUpdateTensor* src, int32_t E, int32_t C, int32_t h, int32_t w, void* dst, int32_t dst_stride, int32_t c_pad,
+                    void* stream);
+int sgr_update_conv(const SgrUpdateConv* conv, void* stream);
+int sgr_update_forward(const SgrUpdateWeights* weights, const SgrUpdateCall* call, void* scratch, size_t scratch_bytes, void* stream);
+
 /* SE3 ops, batched over n.  Pose = (tx,ty,tz,qx,qy,qz,qw) as in lietorch / depth_video.py:69; tau = (rho, theta). */
 int se3_exp(const float* tau, int64_t n, float* pose_out, void* stream);
 int se3_log(const float* pose, int64_t n, float* tau_out, void* stream);

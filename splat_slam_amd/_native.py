@@ -136,6 +136,38 @@ class SgrDspoProblem(C.Structure):
                 ("lm", C.c_float), ("ep", C.c_float), ("alpha", C.c_float), ("dwq", _fp), ("dz", _fp)]
 
 
+class SgrUpdateTensor(C.Structure):
+    _fields_ = [("data", _fp), ("stride", C.c_int64 * 4), ("dtype", C.c_int32)]
+
+
+class SgrUpdateConv(C.Structure):
+    _fields_ = [("src0", _fp), ("src1", _fp), ("stride0", C.c_int32), ("stride1", C.c_int32), ("split", C.c_int32), ("cin", C.c_int32),
+                ("ksize", C.c_int32), ("E", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("weight", _fp), ("weight_elems", C.c_int64),
+                ("bias", _fp), ("cout", C.c_int32), ("act", C.c_int32), ("eadd", _fp), ("eadd_stride", C.c_int32), ("aux0", _fp),
+                ("aux1", _fp), ("aux0_stride", C.c_int32), ("aux1_stride", C.c_int32), ("out", _fp), ("out2", _fp),
+                ("out_kind", C.c_int32), ("out_stride", C.c_int32), ("out2_stride", C.c_int32)]
+
+
+class SgrUpdateLayer(C.Structure):
+    _fields_ = [("weight", _fp), ("weight_elems", C.c_int64), ("bias", _fp)]
+
+
+SGR_UPDATE_LAYERS, SGR_UPDATE_LAUNCHES = 14, 17
+
+
+class SgrUpdateWeights(C.Structure):
+    _fields_ = [("layer", SgrUpdateLayer * SGR_UPDATE_LAYERS), ("glo_weight", _fp), ("glo_bias", _fp)]
+
+
+class SgrUpdateCall(C.Structure):
+    _fields_ = [("net", SgrUpdateTensor), ("inp", SgrUpdateTensor), ("corr", SgrUpdateTensor), ("flow", SgrUpdateTensor),
+                ("E", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("K", C.c_int32), ("ix", _fp), ("net_out", _fp), ("delta", _fp),
+                ("weight", _fp), ("eta", _fp), ("upmask", _fp), ("first_launch", C.c_int32), ("last_launch", C.c_int32)]
+
+
+SGR_UPDATE_F32, SGR_UPDATE_F16 = 0, 1
+SGR_UPDATE_ACTS = {"none": 0, "relu": 1, "sigmoid": 2, "tanh": 3}
+SGR_UPDATE_OUT_NCHW_F16, SGR_UPDATE_OUT_NCHW_F32 = 2, 3
 SGR_DBA_MAX_WINDOW = 512
 SGR_DSPO_WEIGHTS_NONE, SGR_DSPO_WEIGHTS_F32, SGR_DSPO_WEIGHTS_U8 = 0, 1, 2
 SGR_CORR_F32, SGR_CORR_F16 = 0, 1
@@ -246,6 +278,10 @@ SIGNATURES = {
     "sgr_graph_select_proximity": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                              C.c_int32, _fp, C.c_int32, _fp, _fp, C.c_size_t, _fp]),
     "sgr_graph_select_backend": (C.c_int, [_fp] + [C.c_int32] * 6 + [C.c_float, C.c_int32, _fp, C.c_int32, _fp, _fp, C.c_size_t, _fp]),
+    "sgr_update_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "sgr_update_pack": (C.c_int, [C.POINTER(SgrUpdateTensor)] + [C.c_int32] * 4 + [_fp, C.c_int32, C.c_int32, _fp]),
+    "sgr_update_conv": (C.c_int, [C.POINTER(SgrUpdateConv), _fp]),
+    "sgr_update_forward": (C.c_int, [C.POINTER(SgrUpdateWeights), C.POINTER(SgrUpdateCall), _fp, C.c_size_t, _fp]),
     "se3_exp": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_log": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_inv": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
