@@ -882,7 +882,71 @@ int sgr_update_pack(const SgrUpdateTensor* src, int32_t E, int32_t C, int32_t h,
 int sgr_update_conv(const SgrUpdateConv* conv, void* stream);
 int sgr_update_forward(const SgrUpdateWeights* weights, const SgrUpdateCall* call, void* scratch, size_t scratch_bytes, void* stream);
 
-/* SE3 ops, batched over n.  Pose = (tx,ty,tz,qx,qy,qz,qw) as in lietorch / depth_video.py:69; tau = (rho, theta). */
+/* The feature and context encoders of the tracker (BasicEncoder, thirdparty/glorie_slam/modules/droid_net/extractor.py: fnet with
+ * InstanceNorm2d, cnet without a norm), inference only.  Stated in DESIGN.md section 3, "Encoders".  Everything is stream-ordered,
+ * allocates nothing, synchronises nothing and is bitwise reproducible; image i of a batch gives the bits of that image alone.
+ * Activations are channels-last fp16 [image][y][x][channel] as in the update operator.  The output map of a stride-s convolution is
+ * ((h - 1) / s + 1) x ((w - 1) / s + 1); h * w of one image must fit int32, n <= 65535.
+ * sgr_encoder_pack: src [n,3,H,W] with element strides -> dst [n*H*W][8] fp16, channels 3..7 zero; with mean and std (3 host floats
+ * each, or both NULL) the value stored is (x - mean[c]) / std[c], evaluated in fp32.
+ * sgr_encoder_conv: zero padding (ksize - 1) / 2, ksize 1, 3 or 7, stride 1 or 2, cin a multiple of 8, cout 32, 64, 128 or 256.  weight
+ * is fp16 [cout][round_up(ksize^2 * cin, 32)], k = tap * cin + c, padding zero; bias fp32 [cout], 16-byte aligned.  Without a norm:
+ * v = act(sum + bias), act NONE or RELU, then with a residual map (channels-last fp16) v = relu(residual + v); out_kind is one of
+ * SGR_UPDATE_OUT_*.  act SPLIT (cout = 256): channel c < 128 writes tanh(v) to out[image][c][pixel], the others relu(v) to
+ * out2[image][c - 128][pixel], both NCHW fp16.  With norm = INSTANCE (cout <= 128, channels-last out, act NONE or RELU): the first launch
+ * writes the bias-free fp32 sums to raw [n*ho*wo][cout] and per-tile statistics to stats [n][ceil(ho*wo / 128)][cout][4]; the second
+ * merges the statistics in fp64 in a fixed order and writes relu?(residual + act((v - mean) * rstd)), InstanceNorm2d's biased variance
+ * and eps = 1e-5.  The bias is not read: it cancels.
+ * sgr_encoder_forward: a whole encoder.  layer[] order: conv1, layer1.0.conv1, layer1.0.conv2, layer1.1.conv1, layer1.1.conv2,
+ * layer2.0.conv1, layer2.0.conv2, layer2.0.downsample.0, layer2.1.conv1, layer2.1.conv2, layer3.0.conv1, layer3.0.conv2,
+ * layer3.0.downsample.0, layer3.1.conv1, layer3.1.conv2, conv2; conv1's input channels padded to 8.  With norm = INSTANCE every layer
+ * but conv2 is normalised.  out is [n,out_dim,h,w] fp16, or with split (out_dim = 256) out = tanh of channels 0..127 and out2 = relu
+ * of channels 128..255, each [n,128,h,w] fp16.  Only the launches first_launch <= i <= last_launch are enqueued (32 with a norm, 17
+ * without).  scratch: sgr_encoder_scratch_bytes(n, H, W, out_dim, norm) bytes, 16-byte aligned (0 = unsupported sizes, among them a
+ * normalised map of a single element). */
+#define SGR_ENCODER_NORM_NONE 0
+#define SGR_ENCODER_NORM_INSTANCE 1
+#define SGR_ENCODER_ACT_NONE 0
+#define SGR_ENCODER_ACT_RELU 1
+#define SGR_ENCODER_ACT_SPLIT 2
+#define SGR_ENCODER_LAYERS 16
+typedef struct SgrEncoderConv {
+  const void* src;
+  int32_t src_stride, cin, ksize, stride;
+  int32_t n, h, w;                 /* the input maps */
+  const void* weight;
+  int64_t weight_elems;
+  const float* bias;
+  int32_t cout, norm, act;
+  const void* residual;            /* [n*ho*wo][residual_stride] fp16 or NULL */
+  int32_t residual_stride;
+  void* out;
+  void* out2;
+  int32_t out_kind, out_stride;
+  float* raw;                      /* norm only */
+  int64_t raw_elems;
+  float* stats;                    /* norm only */
+  int64_t stats_elems;
+} SgrEncoderConv;
+typedef struct SgrEncoderWeights {
+  SgrUpdateLayer layer[SGR_ENCODER_LAYERS];
+  int32_t out_dim, norm;
+} SgrEncoderWeights;
+typedef struct SgrEncoderCall {
+  SgrUpdateTensor images;          /* [n,3,H,W] */
+  int32_t n, H, W, normalize;
+  float mean[3], std_[3];          /* read when normalize != 0 */
+  void* out;
+  void* out2;
+  int32_t split, first_launch, last_launch;
+} SgrEncoderCall;
+size_t sgr_encoder_scratch_bytes(int32_t n, int32_t H, int32_t W, int32_t out_dim, int32_t norm);
+int sgr_encoder_pack(const SgrUpdateTensor* src, int32_t n, int32_t H, int32_t W, const float* mean, const float* std_, void* dst,
+                     void* stream);
+int sgr_encoder_conv(const SgrEncoderConv* conv, void* stream);
+int sgr_encoder_forward(const SgrEncoderWeights* weights, const SgrEncoderCall* call, void* scratch, size_t scratch_bytes, void* stream);
+
+/* SE3 ops, batched over n.  Pose =(tx,ty,tz,qx,qy,qz,qw) as in lietorch / depth_video.py:69; tau = (rho, theta). */
 int se3_exp(const float* tau, int64_t n, float* pose_out, void* stream);
 int se3_log(const float* pose, int64_t n, float* tau_out, void* stream);
 int se3_inv(const float* pose, int64_t n, float* pose_out, void* stream);

@@ -165,6 +165,31 @@ class SgrUpdateCall(C.Structure):
                 ("weight", _fp), ("eta", _fp), ("upmask", _fp), ("first_launch", C.c_int32), ("last_launch", C.c_int32)]
 
 
+class SgrEncoderConv(C.Structure):
+    _fields_ = [("src", _fp), ("src_stride", C.c_int32), ("cin", C.c_int32), ("ksize", C.c_int32), ("stride", C.c_int32), ("n", C.c_int32),
+                ("h", C.c_int32), ("w", C.c_int32), ("weight", _fp), ("weight_elems", C.c_int64), ("bias", _fp), ("cout", C.c_int32),
+                ("norm", C.c_int32), ("act", C.c_int32), ("residual", _fp), ("residual_stride", C.c_int32), ("out", _fp), ("out2", _fp),
+                ("out_kind", C.c_int32), ("out_stride", C.c_int32), ("raw", _fp), ("raw_elems", C.c_int64), ("stats", _fp),
+                ("stats_elems", C.c_int64)]
+
+
+SGR_ENCODER_LAYERS = 16
+SGR_ENCODER_LAUNCHES = {0: 17, 1: 32}       # by norm
+
+
+class SgrEncoderWeights(C.Structure):
+    _fields_ = [("layer", SgrUpdateLayer * SGR_ENCODER_LAYERS), ("out_dim", C.c_int32), ("norm", C.c_int32)]
+
+
+class SgrEncoderCall(C.Structure):
+    _fields_ = [("images", SgrUpdateTensor), ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("normalize", C.c_int32),
+                ("mean", C.c_float * 3), ("std_", C.c_float * 3), ("out", _fp), ("out2", _fp), ("split", C.c_int32),
+                ("first_launch", C.c_int32), ("last_launch", C.c_int32)]
+
+
+SGR_ENCODER_NORM_NONE, SGR_ENCODER_NORM_INSTANCE = 0, 1
+SGR_ENCODER_ACTS = {"none": 0, "relu": 1, "split": 2}
+SGR_UPDATE_OUT_CL_F16, SGR_UPDATE_OUT_CL_F32 = 0, 1
 SGR_UPDATE_F32, SGR_UPDATE_F16 = 0, 1
 SGR_UPDATE_ACTS = {"none": 0, "relu": 1, "sigmoid": 2, "tanh": 3}
 SGR_UPDATE_OUT_NCHW_F16, SGR_UPDATE_OUT_NCHW_F32 = 2, 3
@@ -282,6 +307,10 @@ SIGNATURES = {
     "sgr_update_pack": (C.c_int, [C.POINTER(SgrUpdateTensor)] + [C.c_int32] * 4 + [_fp, C.c_int32, C.c_int32, _fp]),
     "sgr_update_conv": (C.c_int, [C.POINTER(SgrUpdateConv), _fp]),
     "sgr_update_forward": (C.c_int, [C.POINTER(SgrUpdateWeights), C.POINTER(SgrUpdateCall), _fp, C.c_size_t, _fp]),
+    "sgr_encoder_scratch_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "sgr_encoder_pack": (C.c_int, [C.POINTER(SgrUpdateTensor)] + [C.c_int32] * 3 + [C.POINTER(C.c_float), C.POINTER(C.c_float), _fp, _fp]),
+    "sgr_encoder_conv": (C.c_int, [C.POINTER(SgrEncoderConv), _fp]),
+    "sgr_encoder_forward": (C.c_int, [C.POINTER(SgrEncoderWeights), C.POINTER(SgrEncoderCall), _fp, C.c_size_t, _fp]),
     "se3_exp": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_log": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_inv": (C.c_int, [_fp, C.c_int64, _fp, _fp]),

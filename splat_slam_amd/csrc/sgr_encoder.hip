@@ -1,0 +1,543 @@
+// The tracker's feature and context encoders (BasicEncoder of the reference's thirdparty/glorie_slam/modules/droid_net/extractor.py: fnet with
+// InstanceNorm2d, cnet without a norm), inference only.
+//   sgr_encoder_pack      [n,3,H,W] (fp16 or fp32, any strides), optionally (x - mean[c]) / std[c] -> channels-last fp16, 8 channels per pixel
+//   sgr_encoder_conv      one implicit-GEMM convolution (1x1, 3x3, 7x7; zero padding (k-1)/2; stride 1 or 2) on mfma_f32_16x16x32_f16 with a
+//                         fused epilogue, or, with an instance norm, the raw fp32 sums with per-tile statistics followed by one apply launch
+//   sgr_encoder_forward   a whole encoder: 32 (fnet) or 17 (cnet) stream-ordered launches, no host synchronisation
+// Layouts, the launch list, the rounding points and the statistics scheme are described in DESIGN.md section 3, "Encoders".  The GEMM is
+// that of sgr_update.hip (weights the A operand, pixels the B operand, k = tap * cin + channel) with three differences: a workgroup's 128
+// pixels belong to one image (blockIdx.z), the gather takes a stride, and output channels come in tiles of 32 or 64.  Every sum has a fixed
+// order: no atomics, bitwise reproducible, and image i of a batch gives the bits of that image alone.
+#include <cstdint>
+
+#include "sgr_common.h"
+
+namespace sgr {
+int set_error(int code, const char* fmt, ...);
+
+namespace {
+
+typedef _Float16 half_t;
+typedef __attribute__((ext_vector_type(4))) _Float16 half4;
+typedef __attribute__((ext_vector_type(8))) _Float16 half8;
+typedef __attribute__((ext_vector_type(4))) float floatx4;
+
+constexpr int kThreads = 256;
+constexpr int kBM = 128;                    // output pixels of one workgroup: 4 waves x 2 tiles of 16
+constexpr int kBK = 32;                     // one MFMA k step
+constexpr int kRow = kBK + 8;               // halfs per LDS row: 80 bytes, so that the 16 rows of a fragment read spread over the banks
+constexpr int kInPad = 8;                   // the 3 image channels padded to one 16-byte chunk
+constexpr int kApplyPixels = 512;           // pixels of one workgroup of the apply launch
+constexpr int kLayers = SGR_ENCODER_LAYERS;
+constexpr float kEps = 1e-5f;
+
+struct ConvArgs {
+  SgrEncoderConv c;
+  int ho, wo, HWo, k_pad, tiles;
+};
+
+// One workgroup: kBM output pixels of image blockIdx.z x BN output channels.  Wave v owns pixels [32v, 32v + 32) as two 16-wide B tiles
+// and all BN / 16 A tiles.  Staging: thread t loads the 16-byte chunk k = 8 (t & 3) of pixel rows t >> 2 and 64 + (t >> 2) and of weight
+// row t >> 2 into registers one k step ahead of the MFMAs that consume the previous step out of LDS.
+template <int KS, int BN>
+__global__ void __launch_bounds__(kThreads) enc_conv_kernel(const ConvArgs a) {
+  constexpr int NT = BN / 16;
+  __shared__ __attribute__((aligned(16))) half_t Xs[kBM * kRow];
+  __shared__ __attribute__((aligned(16))) half_t Ws[BN * kRow];
+  __shared__ float red[2][4][BN];
+  __shared__ float shift[BN];
+  const SgrEncoderConv& c = a.c;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int img = blockIdx.z, m0 = blockIdx.x * kBM, n0 = blockIdx.y * BN;
+  const int kc = tid & 3, srow = tid >> 2;
+  const half_t* src = (const half_t*)c.src + (int64_t)img * c.h * c.w * c.src_stride;
+
+  int iy[2], ix[2];
+  bool pv[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int m = m0 + srow + 64 * i;
+    pv[i] = m < a.HWo;
+    const int mm = pv[i] ? m : 0, oy = mm / a.wo;
+    iy[i] = oy * c.stride;
+    ix[i] = (mm - oy * a.wo) * c.stride;
+  }
+  const bool wv = tid < BN * 4;
+  const half_t* wp = (const half_t*)c.weight + (size_t)(n0 + (wv ? srow : 0)) * a.k_pad + kc * 8;
+
+  int tap = (kc * 8) / c.cin, ch = (kc * 8) % c.cin;       // this thread's chunk of the current k step
+  half8 xr[2], wr;
+  auto gload = [&](int kt) {
+    const int dy = tap / KS - KS / 2, dx = tap % KS - KS / 2;
+    const bool tv = tap < KS * KS;                           // the zero tail of a k_pad that is no multiple of the taps
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int yy = iy[i] + dy, xx = ix[i] + dx;
+      half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (pv[i] && tv && (unsigned)yy < (unsigned)c.h && (unsigned)xx < (unsigned)c.w)
+        v = *(const half8*)(src + ((int64_t)yy * c.w + xx) * c.src_stride + ch);
+      xr[i] = v;
+    }
+    if (wv) wr = *(const half8*)(wp + (size_t)kt * kBK);
+  };
+
+  floatx4 acc[NT][2];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[t][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+
+  const int nk = a.k_pad / kBK;
+  gload(0);
+  for (int kt = 0; kt < nk; ++kt) {
+    *(half8*)&Xs[srow * kRow + kc * 8] = xr[0];
+    *(half8*)&Xs[(srow + 64) * kRow + kc * 8] = xr[1];
+    if (wv) *(half8*)&Ws[srow * kRow + kc * 8] = wr;
+    __syncthreads();
+    if (kt + 1 < nk) {
+      ch += kBK;
+      while (ch >= c.cin) {
+        ch -= c.cin;
+        ++tap;
+      }
+      gload(kt + 1);
+    }
+    half8 bf[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) bf[j] = *(const half8*)&Xs[(wave * 32 + j * 16 + (lane & 15)) * kRow + (lane >> 4) * 8];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const half8 af = *(const half8*)&Ws[(t * 16 + (lane & 15)) * kRow + (lane >> 4) * 8];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[j], acc[t][j], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+
+  // acc[t][j][r] is output channel n0 + 16 t + 4 (lane >> 4) + r of pixel m0 + 32 wave + 16 j + (lane & 15) of this image
+  bool valid[2];
+  int64_t gm[2];                                             // pixel index over the whole batch
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int m = m0 + wave * 32 + j * 16 + (lane & 15);
+    valid[j] = m < a.HWo;
+    gm[j] = (int64_t)img * a.HWo + m;
+  }
+
+  if (c.norm) {
+    // The bias of a normalised convolution cancels: the statistics and the stored sums are those of the bias-free accumulator.  Per
+    // (tile, channel): the count, a shift s = the tile mean rounded to fp32, S1 = sum (v - s) and S2 = sum (v - s)^2.  The 16 pixel
+    // lanes are summed by a butterfly, the 2 x 4 partials of a channel in the order (j, wave).
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (!valid[j]) continue;
+#pragma unroll
+      for (int t = 0; t < NT; ++t) *(floatx4*)&c.raw[gm[j] * c.cout + n0 + t * 16 + (lane >> 4) * 4] = acc[t][j];
+    }
+    const float cnt = (float)min(kBM, a.HWo - m0);
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float s = (valid[0] ? acc[t][0][r] : 0.f) + (valid[1] ? acc[t][1][r] : 0.f);
+#pragma unroll
+        for (int d = 1; d < 16; d <<= 1) s += __shfl_xor(s, d);
+        if ((lane & 15) == 0) red[0][wave][t * 16 + (lane >> 4) * 4 + r] = s;
+      }
+    __syncthreads();
+    if (tid < BN) shift[tid] = (((red[0][0][tid] + red[0][1][tid]) + red[0][2][tid]) + red[0][3][tid]) / cnt;
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int n = t * 16 + (lane >> 4) * 4 + r;
+        const float sh = shift[n];
+        const float d0 = valid[0] ? acc[t][0][r] - sh : 0.f, d1 = valid[1] ? acc[t][1][r] - sh : 0.f;
+        float s1 = d0 + d1, s2 = d0 * d0 + d1 * d1;
+#pragma unroll
+        for (int d = 1; d < 16; d <<= 1) {
+          s1 += __shfl_xor(s1, d);
+          s2 += __shfl_xor(s2, d);
+        }
+        if ((lane & 15) == 0) {
+          red[0][wave][n] = s1;
+          red[1][wave][n] = s2;
+        }
+      }
+    __syncthreads();
+    if (tid < BN) {
+      const float s1 = ((red[0][0][tid] + red[0][1][tid]) + red[0][2][tid]) + red[0][3][tid];
+      const float s2 = ((red[1][0][tid] + red[1][1][tid]) + red[1][2][tid]) + red[1][3][tid];
+      *(floatx4*)&c.stats[(((int64_t)img * a.tiles + blockIdx.x) * c.cout + n0 + tid) * 4] = floatx4{cnt, shift[tid], s1, s2};
+    }
+    return;
+  }
+
+  const half_t* res = (const half_t*)c.residual;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    if (!valid[j]) continue;
+    const int p = (int)(gm[j] - (int64_t)img * a.HWo);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int nb = n0 + t * 16 + (lane >> 4) * 4;
+      floatx4 v = acc[t][j] + *(const floatx4*)&c.bias[nb];
+      if (c.act == SGR_ENCODER_ACT_SPLIT) {                  // cout = 256: tanh(net) | relu(inp), two NCHW fp16 tensors
+        const bool lo = nb < 128;
+        half_t* dst = (half_t*)(lo ? c.out : c.out2) + ((int64_t)img * 128 + (lo ? nb : nb - 128)) * a.HWo + p;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dst[(int64_t)r * a.HWo] = (half_t)(lo ? tanhf(v[r]) : fmaxf(v[r], 0.f));
+        continue;
+      }
+      if (c.act == SGR_ENCODER_ACT_RELU)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
+      if (res) {
+        const half4 x = *(const half4*)&res[gm[j] * c.residual_stride + nb];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = fmaxf((float)x[r] + v[r], 0.f);
+      }
+      switch (c.out_kind) {
+        case SGR_UPDATE_OUT_CL_F16: {
+          half4 o;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) o[r] = (half_t)v[r];
+          *(half4*)&((half_t*)c.out)[gm[j] * c.out_stride + nb] = o;
+          break;
+        }
+        case SGR_UPDATE_OUT_CL_F32: *(floatx4*)&((float*)c.out)[gm[j] * c.out_stride + nb] = v; break;
+        case SGR_UPDATE_OUT_NCHW_F16:
+#pragma unroll
+          for (int r = 0; r < 4; ++r) ((half_t*)c.out)[((int64_t)img * c.cout + nb + r) * a.HWo + p] = (half_t)v[r];
+          break;
+        default:
+#pragma unroll
+          for (int r = 0; r < 4; ++r) ((float*)c.out)[((int64_t)img * c.cout + nb + r) * a.HWo + p] = v[r];
+          break;
+      }
+    }
+  }
+}
+
+struct ApplyArgs {
+  const float* raw;
+  const float* stats;
+  const half_t* res;
+  void* out;
+  int HWo, tiles, C, relu, res_stride, out_f32, out_stride;
+};
+
+// The second launch of a normalised convolution, grid (pixel blocks, images).  Every workgroup first merges the per-tile statistics of
+// its image in fp64 about s0, the shift of tile 0: with d = s_i - s0, A = sum (n_i d + S1_i) and B = sum (S2_i + 2 d S1_i + n_i d^2) are
+// the sums of (v - s0) and (v - s0)^2 over the map, so mean = s0 + A / N and M2 = B - A^2 / N.  Thread (slot, channel) takes the tiles
+// slot, slot + S, ... (S = 256 / C) in ascending order, the slots are then added in ascending order: the result depends on the map alone.
+// mean and 1 / sqrt(M2 / N + eps) are rounded once to fp32; then y = (v - mean) * rstd, ReLU, + residual, ReLU in fp32, one rounding to
+// the output.  One thread per (pixel, 8 channels).
+__global__ void __launch_bounds__(kThreads) enc_apply_kernel(const ApplyArgs a) {
+  __shared__ double pa[kThreads], pb[kThreads];
+  __shared__ float mu[128], rs[128];
+  const int tid = threadIdx.x, img = blockIdx.y, C = a.C;
+  {
+    const int ch = tid % C, slot = tid / C, S = kThreads / C;
+    const floatx4* st = (const floatx4*)a.stats + (int64_t)img * a.tiles * C;
+    const double s0 = (double)st[ch][1];
+    double A = 0.0, B = 0.0;
+    for (int t = slot; t < a.tiles; t += S) {
+      const floatx4 q = st[(int64_t)t * C + ch];
+      const double n = q[0], d = (double)q[1] - s0, s1 = q[2], s2 = q[3];
+      A += n * d + s1;
+      B += s2 + 2.0 * d * s1 + n * d * d;
+    }
+    pa[tid] = A;
+    pb[tid] = B;
+    __syncthreads();
+    if (tid < C) {
+      for (int s = 1; s < S; ++s) {
+        A += pa[s * C + tid];
+        B += pb[s * C + tid];
+      }
+      const double N = (double)a.HWo, mean = s0 + A / N, var = fmax((B - A * A / N) / N, 0.0);
+      mu[tid] = (float)mean;
+      rs[tid] = (float)(1.0 / sqrt(var + (double)kEps));
+    }
+    __syncthreads();
+  }
+  const int chunks = C / 8, p0 = blockIdx.x * kApplyPixels;
+  for (int i = tid; i < kApplyPixels * chunks; i += kThreads) {
+    const int p = p0 + i / chunks, j = i % chunks;
+    if (p >= a.HWo) break;
+    const int64_t m = (int64_t)img * a.HWo + p;
+    const floatx4 lo = *(const floatx4*)&a.raw[m * C + j * 8], hi = *(const floatx4*)&a.raw[m * C + j * 8 + 4];
+    float v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      v[k] = ((k < 4 ? lo[k] : hi[k - 4]) - mu[j * 8 + k]) * rs[j * 8 + k];
+      if (a.relu) v[k] = fmaxf(v[k], 0.f);
+    }
+    if (a.res) {
+      const half8 x = *(const half8*)&a.res[m * a.res_stride + j * 8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = fmaxf((float)x[k] + v[k], 0.f);
+    }
+    if (a.out_f32) {
+      float* o = (float*)a.out + m * a.out_stride + j * 8;
+      *(floatx4*)o = floatx4{v[0], v[1], v[2], v[3]};
+      *(floatx4*)(o + 4) = floatx4{v[4], v[5], v[6], v[7]};
+    } else {
+      half8 o;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) o[k] = (half_t)v[k];
+      *(half8*)&((half_t*)a.out)[m * a.out_stride + j * 8] = o;
+    }
+  }
+}
+
+struct PackArgs {
+  SgrUpdateTensor src;
+  float mean[3], inv_on, std_[3];
+  int HW, w;
+};
+
+// One thread per pixel: three strided reads, one 16-byte store (channels 3..7 zero).  (x - mean) / std is the fp32 expression torch
+// evaluates for sub then div, so normalising here or beforehand gives the same fp16 values.
+__global__ void __launch_bounds__(kThreads) enc_pack_kernel(const PackArgs a, half_t* __restrict__ dst) {
+  const int p = blockIdx.x * kThreads + threadIdx.x, img = blockIdx.y;
+  if (p >= a.HW) return;
+  const int y = p / a.w, x = p - y * a.w;
+  const int64_t base = img * a.src.stride[0] + y * a.src.stride[2] + x * a.src.stride[3];
+  half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const int64_t o = base + ch * a.src.stride[1];
+    float f = a.src.dtype == SGR_UPDATE_F16 ? (float)((const half_t*)a.src.data)[o] : ((const float*)a.src.data)[o];
+    if (a.inv_on != 0.f) f = (f - a.mean[ch]) / a.std_[ch];
+    v[ch] = (half_t)f;
+  }
+  *(half8*)&dst[((int64_t)img * a.HW + p) * kInPad] = v;
+}
+
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+inline int out_size(int v, int stride) { return (v - 1) / stride + 1; }
+inline int tiles_of(int64_t hw) { return (int)((hw + kBM - 1) / kBM); }
+
+bool map_ok(int n, int h, int w) { return n >= 1 && n <= 65535 && h >= 1 && w >= 1 && (int64_t)h * w <= 0x7fffffff - kBM; }
+
+int launch_conv(const SgrEncoderConv& c, hipStream_t stream) {
+  if (!c.src || !c.weight || !c.bias) return set_error(SGR_ERR_INVALID, "encoder_conv: null argument");
+  if (!map_ok(c.n, c.h, c.w) || c.cin < 8 || c.cin % 8)
+    return set_error(SGR_ERR_INVALID, "encoder_conv: bad sizes (n=%d h=%d w=%d cin=%d); n <= 65535, cin a positive multiple of 8", c.n, c.h, c.w,
+                     c.cin);
+  if (c.cout != 32 && c.cout != 64 && c.cout != 128 && c.cout != 256)
+    return set_error(SGR_ERR_INVALID, "encoder_conv: cout %d is not 32, 64, 128 or 256", c.cout);
+  if (c.ksize != 1 && c.ksize != 3 && c.ksize != 7) return set_error(SGR_ERR_INVALID, "encoder_conv: kernel size %d is not 1, 3 or 7", c.ksize);
+  if (c.stride != 1 && c.stride != 2) return set_error(SGR_ERR_INVALID, "encoder_conv: stride %d is not 1 or 2", c.stride);
+  if (c.src_stride < c.cin || c.src_stride % 8 || !aligned16(c.src))
+    return set_error(SGR_ERR_INVALID, "encoder_conv: src needs a 16-byte aligned base and a stride (%d) that is a multiple of 8 and >= %d",
+                     c.src_stride, c.cin);
+  const int k_pad = round_up(c.ksize * c.ksize * c.cin, kBK);
+  if (c.weight_elems < (int64_t)c.cout * k_pad || !aligned16(c.weight) || !aligned16(c.bias))
+    return set_error(SGR_ERR_INVALID, "encoder_conv: packed weights must be 16-byte aligned [%d][%d] fp16, got %lld elements", c.cout, k_pad,
+                     (long long)c.weight_elems);
+  if (c.act < SGR_ENCODER_ACT_NONE || c.act > SGR_ENCODER_ACT_SPLIT) return set_error(SGR_ERR_INVALID, "encoder_conv: unknown epilogue %d", c.act);
+  if (c.residual && (c.residual_stride < c.cout || c.residual_stride % 8 || !aligned16(c.residual)))
+    return set_error(SGR_ERR_INVALID, "encoder_conv: residual needs a 16-byte aligned base and a stride (%d) that is a multiple of 8 and >= %d",
+                     c.residual_stride, c.cout);
+  if (!c.out || !aligned16(c.out)) return set_error(SGR_ERR_INVALID, "encoder_conv: out must be 16-byte aligned");
+  ConvArgs a;
+  a.c = c;
+  a.ho = out_size(c.h, c.stride), a.wo = out_size(c.w, c.stride);
+  a.HWo = a.ho * a.wo;
+  a.k_pad = k_pad;
+  a.tiles = tiles_of(a.HWo);
+  if (c.act == SGR_ENCODER_ACT_SPLIT) {
+    if (c.cout != 256 || c.norm || c.residual || !c.out2)
+      return set_error(SGR_ERR_INVALID, "encoder_conv: the tanh | relu split needs cout = 256, out2, no norm and no residual");
+  } else {
+    if (c.out_kind < SGR_UPDATE_OUT_CL_F16 || c.out_kind > SGR_UPDATE_OUT_NCHW_F32)
+      return set_error(SGR_ERR_INVALID, "encoder_conv: unknown output kind %d", c.out_kind);
+    if (c.out_kind <= SGR_UPDATE_OUT_CL_F32 && (c.out_stride < c.cout || c.out_stride % 8))
+      return set_error(SGR_ERR_INVALID, "encoder_conv: out_stride %d must be a multiple of 8 and >= cout %d", c.out_stride, c.cout);
+  }
+  if (c.norm) {
+    const int64_t M = (int64_t)c.n * a.HWo;
+    if (c.norm != SGR_ENCODER_NORM_INSTANCE || c.cout > 128 || c.out_kind > SGR_UPDATE_OUT_CL_F32)
+      return set_error(SGR_ERR_INVALID, "encoder_conv: a normalised convolution has cout <= 128 and a channels-last output");
+    if (!c.raw || !c.stats || !aligned16(c.raw) || !aligned16(c.stats) || c.raw_elems < M * c.cout ||
+        c.stats_elems < (int64_t)c.n * a.tiles * c.cout * 4)
+      return set_error(SGR_ERR_WORKSPACE, "encoder_conv: a normalised convolution needs raw fp32 [%lld][%d] and stats fp32 [%d][%d][%d][4]",
+                       (long long)M, c.cout, c.n, a.tiles, c.cout);
+  }
+  const int bn = c.cout == 32 ? 32 : 64;
+  const dim3 grid((unsigned)a.tiles, (unsigned)(c.cout / bn), (unsigned)c.n), block(kThreads);
+#define SGR_ENCODER_LAUNCH(KS)                                                                  \
+  if (bn == 32)                                                                                 \
+    hipLaunchKernelGGL((enc_conv_kernel<KS, 32>), grid, block, 0, stream, a);                   \
+  else                                                                                          \
+    hipLaunchKernelGGL((enc_conv_kernel<KS, 64>), grid, block, 0, stream, a)
+  if (c.ksize == 1) {
+    SGR_ENCODER_LAUNCH(1);
+  } else if (c.ksize == 3) {
+    SGR_ENCODER_LAUNCH(3);
+  } else {
+    SGR_ENCODER_LAUNCH(7);
+  }
+#undef SGR_ENCODER_LAUNCH
+  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "encoder_conv launch failed");
+}
+
+// (the arguments were validated by launch_conv of the same record)
+int launch_apply(const SgrEncoderConv& c, hipStream_t stream) {
+  ApplyArgs a;
+  a.raw = c.raw, a.stats = c.stats, a.res = (const half_t*)c.residual, a.out = c.out;
+  a.HWo = out_size(c.h, c.stride) * out_size(c.w, c.stride);
+  a.tiles = tiles_of(a.HWo);
+  a.C = c.cout, a.relu = c.act == SGR_ENCODER_ACT_RELU, a.res_stride = c.residual_stride;
+  a.out_f32 = c.out_kind == SGR_UPDATE_OUT_CL_F32, a.out_stride = c.out_stride;
+  const dim3 grid((unsigned)((a.HWo + kApplyPixels - 1) / kApplyPixels), (unsigned)c.n);
+  hipLaunchKernelGGL(enc_apply_kernel, grid, dim3(kThreads), 0, stream, a);
+  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "encoder_conv: apply launch failed");
+}
+
+int launch_pack(const SgrUpdateTensor& src, int n, int H, int W, const float* mean, const float* std_, half_t* dst, hipStream_t stream) {
+  PackArgs a;
+  a.src = src;
+  a.inv_on = mean ? 1.f : 0.f;
+  for (int i = 0; i < 3; ++i) a.mean[i] = mean ? mean[i] : 0.f, a.std_[i] = mean ? std_[i] : 1.f;
+  a.HW = H * W, a.w = W;
+  hipLaunchKernelGGL(enc_pack_kernel, dim3((unsigned)((a.HW + kThreads - 1) / kThreads), (unsigned)n), dim3(kThreads), 0, stream, a, dst);
+  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "encoder_pack launch failed");
+}
+
+// The maps of a call: level 0 the image, level 1 after the stem (32 channels), 2 after layer2 (64), 3 after layer3 (128).
+struct Plan {
+  int h[4], w[4];
+  half_t *xin, *act[4];
+  float *raw, *stats;
+  int64_t raw_elems, stats_elems;
+  size_t bytes;
+};
+Plan carve(void* base, int n, int H, int W, bool norm) {
+  Plan s;
+  s.h[0] = H, s.w[0] = W;
+  for (int l = 1; l < 4; ++l) s.h[l] = out_size(s.h[l - 1], 2), s.w[l] = out_size(s.w[l - 1], 2);
+  size_t off = 0;
+  auto take = [&](size_t nbytes) {
+    void* p = base ? (char*)base + off : nullptr;
+    off += align256(nbytes);
+    return p;
+  };
+  int64_t act_elems = 0;
+  s.raw_elems = s.stats_elems = 0;
+  for (int l = 1; l < 4; ++l) {
+    const int64_t hw = (int64_t)s.h[l] * s.w[l], ch = 16 << l;
+    act_elems = act_elems > n * hw * ch ? act_elems : n * hw * ch;
+    const int64_t st = (int64_t)n * tiles_of(hw) * ch * 4;
+    s.stats_elems = s.stats_elems > st ? s.stats_elems : st;
+  }
+  s.raw_elems = act_elems;
+  s.xin = (half_t*)take((size_t)n * H * W * kInPad * 2);
+  for (int i = 0; i < 4; ++i) s.act[i] = (half_t*)take((size_t)act_elems * 2);
+  s.raw = (float*)take(norm ? (size_t)s.raw_elems * 4 : 0);
+  s.stats = (float*)take(norm ? (size_t)s.stats_elems * 4 : 0);
+  s.bytes = off;
+  return s;
+}
+
+bool sizes_ok(int n, int H, int W, int out_dim, int norm) {
+  if (!map_ok(n, H, W) || (out_dim != 128 && out_dim != 256) || (norm != SGR_ENCODER_NORM_NONE && norm != SGR_ENCODER_NORM_INSTANCE)) return false;
+  if ((int64_t)n * H * W > ((int64_t)1 << 40)) return false;
+  const int h3 = out_size(out_size(out_size(H, 2), 2), 2), w3 = out_size(out_size(out_size(W, 2), 2), 2);
+  return !norm || (int64_t)h3 * w3 > 1;             // an instance norm over one element is undefined (torch raises as well)
+}
+
+}  // namespace
+}  // namespace sgr
+
+using namespace sgr;
+
+extern "C" {
+
+size_t sgr_encoder_scratch_bytes(int32_t n, int32_t H, int32_t W, int32_t out_dim, int32_t norm) {
+  if (!sizes_ok(n, H, W, out_dim, norm)) return 0;
+  return carve(nullptr, n, H, W, norm != 0).bytes;
+}
+
+int sgr_encoder_pack(const SgrUpdateTensor* src, int32_t n, int32_t H, int32_t W, const float* mean, const float* std_, void* dst, void* stream) {
+  if (!src || !src->data || !dst || !aligned16(dst)) return set_error(SGR_ERR_INVALID, "encoder_pack: null or unaligned argument");
+  if (!map_ok(n, H, W)) return set_error(SGR_ERR_INVALID, "encoder_pack: bad sizes (n=%d H=%d W=%d)", n, H, W);
+  if (src->dtype != SGR_UPDATE_F16 && src->dtype != SGR_UPDATE_F32) return set_error(SGR_ERR_INVALID, "encoder_pack: unknown dtype");
+  if ((mean != nullptr) != (std_ != nullptr)) return set_error(SGR_ERR_INVALID, "encoder_pack: mean and std come together");
+  return launch_pack(*src, n, H, W, mean, std_, (half_t*)dst, (hipStream_t)stream);
+}
+
+int sgr_encoder_conv(const SgrEncoderConv* conv, void* stream) {
+  if (!conv) return set_error(SGR_ERR_INVALID, "encoder_conv: null argument");
+  const int rc = launch_conv(*conv, (hipStream_t)stream);
+  if (rc != SGR_OK || !conv->norm) return rc;
+  return launch_apply(*conv, (hipStream_t)stream);
+}
+
+int sgr_encoder_forward(const SgrEncoderWeights* wt, const SgrEncoderCall* call, void* scratch, size_t scratch_bytes, void* stream_) {
+  if (!wt || !call || !scratch) return set_error(SGR_ERR_INVALID, "encoder_forward: null argument");
+  const int n = call->n, H = call->H, W = call->W, norm = wt->norm, out_dim = wt->out_dim;
+  if (!sizes_ok(n, H, W, out_dim, norm))
+    return set_error(SGR_ERR_INVALID, "encoder_forward: unsupported sizes (n=%d H=%d W=%d out_dim=%d norm=%d)", n, H, W, out_dim, norm);
+  if (!call->images.data || !call->out) return set_error(SGR_ERR_INVALID, "encoder_forward: null tensor");
+  if (call->images.dtype != SGR_UPDATE_F16 && call->images.dtype != SGR_UPDATE_F32) return set_error(SGR_ERR_INVALID, "encoder_forward: unknown dtype");
+  if (call->split && (out_dim != 256 || !call->out2)) return set_error(SGR_ERR_INVALID, "encoder_forward: the split output needs out_dim = 256 and out2");
+  for (int i = 0; i < kLayers; ++i)
+    if (!wt->layer[i].weight || !wt->layer[i].bias) return set_error(SGR_ERR_INVALID, "encoder_forward: null weights");
+  const Plan s = carve(scratch, n, H, W, norm != 0);
+  if (scratch_bytes < s.bytes || !aligned16(scratch))
+    return set_error(SGR_ERR_WORKSPACE, "encoder_forward: scratch of %zu bytes, need %zu (16-byte aligned)", scratch_bytes, s.bytes);
+  hipStream_t stream = (hipStream_t)stream_;
+  int launch = -1, rc = SGR_OK;
+  auto on = [&]() {
+    ++launch;
+    return launch >= call->first_launch && launch <= call->last_launch;
+  };
+  // one convolution of the list: with a norm two launches (sums + statistics, apply), otherwise one
+  auto conv = [&](int layer, const half_t* src, int cin, int lvl_in, int ks, int stride, int cout, int act, const half_t* res, void* out,
+                  int out_kind, void* out2) -> int {
+    SgrEncoderConv c = {};
+    c.src = src, c.src_stride = cin, c.cin = cin, c.ksize = ks, c.stride = stride, c.n = n, c.h = s.h[lvl_in], c.w = s.w[lvl_in];
+    c.weight = wt->layer[layer].weight, c.weight_elems = wt->layer[layer].weight_elems, c.bias = wt->layer[layer].bias;
+    c.cout = cout, c.act = act, c.residual = res, c.residual_stride = cout;
+    c.out = out, c.out2 = out2, c.out_kind = out_kind, c.out_stride = cout;
+    const bool normed = norm && layer != kLayers - 1;
+    c.norm = normed ? norm : SGR_ENCODER_NORM_NONE;
+    c.raw = normed ? s.raw : nullptr, c.raw_elems = s.raw_elems, c.stats = normed ? s.stats : nullptr, c.stats_elems = s.stats_elems;
+    if (on() && (rc = launch_conv(c, stream))) return rc;
+    if (normed && on() && (rc = launch_apply(c, stream))) return rc;
+    return SGR_OK;
+  };
+  const int CL = SGR_UPDATE_OUT_CL_F16, NONE = SGR_ENCODER_ACT_NONE, RELU = SGR_ENCODER_ACT_RELU;
+  if (on() && (rc = launch_pack(call->images, n, H, W, call->normalize ? call->mean : nullptr, call->normalize ? call->std_ : nullptr, s.xin, stream)))
+    return rc;
+  if ((rc = conv(0, s.xin, kInPad, 0, 7, 2, 32, RELU, nullptr, s.act[0], CL, nullptr))) return rc;
+  int cur = 0, layer = 1;
+  // a residual block: y = relu(n(conv1(x))), out = relu(x' + relu(n(conv2(y)))), x' = x or n(downsample(x)); x, y, x', out in four buffers
+  auto block = [&](int lvl_in, int cin, int cout, int stride) -> int {
+    const int y = (cur + 1) & 3, xd = (cur + 2) & 3, o = (cur + 3) & 3, lvl = lvl_in + (stride == 2);
+    if ((rc = conv(layer, s.act[cur], cin, lvl_in, 3, stride, cout, RELU, nullptr, s.act[y], CL, nullptr))) return rc;
+    const half_t* skip = s.act[cur];
+    if (stride == 2) {
+      if ((rc = conv(layer + 2, s.act[cur], cin, lvl_in, 1, 2, cout, NONE, nullptr, s.act[xd], CL, nullptr))) return rc;
+      skip = s.act[xd];
+    }
+    if ((rc = conv(layer + 1, s.act[y], cout, lvl, 3, 1, cout, RELU, skip, s.act[o], CL, nullptr))) return rc;
+    layer += stride == 2 ? 3 : 2;
+    cur = o;
+    return SGR_OK;
+  };
+  if ((rc = block(1, 32, 32, 1)) || (rc = block(1, 32, 32, 1))) return rc;
+  if ((rc = block(1, 32, 64, 2)) || (rc = block(2, 64, 64, 1))) return rc;
+  if ((rc = block(2, 64, 128, 2)) || (rc = block(3, 128, 128, 1))) return rc;
+  return conv(kLayers - 1, s.act[cur], 128, 3, 1, 1, out_dim, call->split ? SGR_ENCODER_ACT_SPLIT : NONE, nullptr, call->out,
+              SGR_UPDATE_OUT_NCHW_F16, call->out2);
+}
+
+}  // extern "C"
