@@ -12,7 +12,8 @@ on the gfx950 kernels `sgr_dspo_*` (include/splat_hip.h, csrc/sgr_dspo.hip).  St
         fitting frames (error / mean disparity > mono_thres, NaN, scale < 0, fewer than half the pixels valid)
     depth_scale_step(poses, disps, intrinsics, mono_disps, valid_depth_mask, scales, shifts, n_frames, target, weight, eta, ii, jj,
                      itrs=2, lm=1e-4, ep=0.1, mono_thres=0.1, alpha=0.01) -> any_kept (0-dim bool tensor on the device)
-        the whole stage-2 branch: align_and_mask, itrs iterations of ba_with_scale_shift, the final clamp to >= 1e-5.
+        the whole stage-2 branch: align_and_mask, itrs iterations of ba_with_scale_shift, the final clamp to >= 1e-5.  An edge with a
+        frame outside [0, min(N, len(poses))) takes part in nothing: it moves no frame and does not count as kept.
 
 Poses are (t, q xyzw), world to camera.  Every tensor lives on the GPU; there is no CPU path.  All work goes on the current torch stream
 and nothing synchronises with the host: M is eta.shape[0]; if it differs from the number of distinct ii, nothing is updated and dwq, dz
@@ -206,7 +207,10 @@ def depth_scale_step(poses, disps, intrinsics, mono_disps, valid_depth_mask, sca
     keep = align_and_mask(disps, mono_disps, valid_depth_mask, scales, shifts, n_frames, ii, jj, mono_thres)
     ba_with_scale_shift(target, weight, eta, poses, disps, intrinsics, ii, jj, mono_disps, scales, shifts, valid_depth_mask, 0, lm, ep,
                         alpha, itrs, keep)
+    # an edge with a frame outside [0, nv) takes part in nothing in the kernels: it moves no frame here either
     n = disps.shape[0]
+    nv = min(n, poses.shape[0])
+    keep = keep & (ii >= 0) & (ii < nv) & (jj >= 0) & (jj < nv)
     moved = torch.zeros(n, dtype=torch.int32, device=disps.device).index_add_(0, ii.clamp(0, n - 1), keep.to(torch.int32)) > 0
     disps.copy_(torch.where(moved[:, None, None], disps.clamp(min=1e-5), disps))
     return keep.any()

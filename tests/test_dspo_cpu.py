@@ -199,3 +199,139 @@ def test_oracle_edge_mask_equals_removing_the_edges():
     np.testing.assert_array_equal(a[4][:2], b[4])
     assert np.all(a[3][2] == 0) and np.all(a[4][2] == 0)
     np.testing.assert_array_equal(a[0][2], s["disps"][2])
+
+
+# ---- the oracle with magnitudes and the criteria of tests/dspo_cases.py, proved on the CPU
+import dspo_cases as DC      # noqa: E402
+
+MUTATIONS = {                                   # planted fault -> the smallest case that must show it
+    "thresh_025": "pix:7,9,1.0",                # the depth threshold 0.25 of stage 1 instead of 0.2
+    "targets_chw": "pix:3,5,1.0",               # targets read as [E,2,h,w]
+    "pix_div_ht": "pix:5,13,1.0",               # pixel row and column from p / ht
+    "drop_last_pixel": "pix:3,5,1.0",           # the last pixel left out of the frame sums
+    "drop_last_edge": "pix:7,9,1.0",            # the last kept edge of a frame's run left out
+    "dup_once": "dup",                          # a duplicate edge counted once
+    "count_masked": "mask:bool",                # a masked edge counted
+    "clamp_oob": "oob",                         # an out-of-range edge clamped into range and counted
+    "eta_by_frame": "pix:7,9,1.0",              # eta indexed by frame instead of by depth row
+    "scale_by_row": "pix:7,9,1.0",              # scales and shifts indexed by depth row instead of by frame
+    "gain_on_rd": "pix:7,9,1.0",                # the gain 10 applied to rd
+    "jd_kept": "pix:7,9,1.0",                   # Jd kept where the prior is invalid on a valid-depth pixel
+    "ignore_le": "ignore:some",                 # ignore_frames tested with <=
+    "lm_from_S": "pix:7,9,1.0",                 # the damping lm taken from the reduced S instead of H_diag
+    "sums_fp32": "flat:384,512",                # the seven sums accumulated in fp32: shows where P is far above the units of an addend
+    "S_subtracted_fp32": "far:16,16",           # S = H - sum Q E E^T from fp32 sums: the cancellation the kernel avoids, alpha = 1
+    "nonpd_zero_all": "singular",               # a frame that is not positive definite zeroes every frame's dwq
+    "no_floor": "pix:3,5,1.0",                  # the floor at 0 omitted
+    "dz_prev_row": "pix:7,9,1.0",               # dz back-substituted with the dwq of the previous row
+}
+
+
+def scene_wants(name):
+    return dict(want_between=name.startswith("pix") or name == MUTATIONS["thresh_025"])
+
+
+@pytest.fixture(scope="module")
+def float32_runs():
+    return {name: DC.criteria(name, *DC.emulate(name)) for name in DC.CASES}
+
+
+def test_every_dspo_case_keeps_its_decisions_away_from_fp32_rounding():
+    assert set(MUTATIONS) == set(D.MUTATIONS) and set(MUTATIONS.values()) <= set(DC.CASES)
+    for name in DC.CASES + ["iter"]:
+        DC.check_scene(name, **scene_wants(name))
+    # the edges the cases are there for
+    assert [DC.oracle(f"pix:{h},{w},1.0")["P"] for h, w in DC.PIXEL_SHAPES] == [15, 63, 65, 256, 257]
+    assert [len(DC.case(f"tile:{E}")["ii"]) for E in DC.TILE_E] == [255, 256, 257, 513]
+    for name, nv, M in (("oob", 9, 6), ("oob:long_poses", 9, 6), ("oob:short_poses", 7, 5)):
+        c, o = DC.case(name), DC.oracle(name)
+        assert o["nv"] == nv and o["M"] == M and 8 not in o["kx"] and 8 in c["ii"]
+        assert 0 < len(R.kept_edges(c["ii"], c["jj"], nv)) < len(c["ii"])
+    for name in ("mask:bool", "mask:u8"):
+        o = DC.oracle(name)
+        assert [f for k, f in enumerate(o["kx"]) if not o["active"][k]] == [4, 7]
+    assert sorted(set(DC.case("mask:u8")["keep"].tolist())) == [0, 1, 2, 255] and DC.case("mask:bool")["keep"].dtype == bool
+    assert DC.oracle("one_edge")["M"] == 1 and DC.oracle("big")["nv"] == 1030 and DC.oracle("big")["kx"][:2] == [3, 7]
+    o = DC.oracle("singular")
+    assert [f for k, f in enumerate(o["kx"]) if o["fail"][k]] == [5]
+
+
+def test_float32_restatement_of_dspo_is_inside_every_criterion_at_every_case(float32_runs):
+    worst = {}
+    for name, (ratios, broken) in float32_runs.items():
+        print(f"{name}: err / bound " + " ".join(f"{k}={v:.4f}" for k, v in sorted(ratios.items())), broken)
+        assert not broken, (name, broken)
+        for k, r in ratios.items():
+            assert r <= 1.0, (name, k, r)
+            if r > worst.get(k, (0.0, ""))[0]:
+                worst[k] = (r, name)
+    print("\nlargest err / bound of the float32 restatement (an emulation, not the device):")
+    for k in sorted(worst):
+        print(f"  criterion {k}: {worst[k][0]:.4f} at {worst[k][1]}")
+    assert set(worst) == {"A", "B"}
+    # the singular frame is held to dwq == 0 and still steps its disparities by Q b
+    c, o = DC.case("singular"), DC.oracle("singular")
+    _, _, _, dwq, dz = DC.emulate("singular")
+    k = o["kx"].index(5)
+    assert not dwq[k].any() and np.abs(dz[k]).max() > 1e-4 and np.abs(np.delete(dwq, k, 0)).min() > 0
+
+
+@pytest.mark.parametrize("mutation", list(MUTATIONS))
+def test_planted_dspo_fault_fails_a_criterion(mutation):
+    """sums_fp32 is the one fault that small shapes cannot show: an fp32 sum of P addends costs at most P units of 2^-24 against
+    addends that carry 315 or more of their own, so up to P = 257 it moves criterion A in the fifth digit only.  Its case is the flat
+    384 x 512 frame of tests/dspo_cases.py, where every addition rounds the same way and the drift leaves the bound."""
+    name = MUTATIONS[mutation]
+    ratios, broken = DC.criteria(name, *DC.emulate(name, mutate=mutation))
+    print(mutation, name, ratios, broken)
+    assert not DC.passes(ratios, broken)
+    ratios, broken = DC.criteria(name, *DC.emulate(name))        # ... and it is the fault, not the case, that fails
+    assert DC.passes(ratios, broken)
+
+
+def test_the_derived_dspo_units_are_the_documented_ones():
+    """the counts DESIGN.md section 3 tabulates are what the formulas give: those of a frame with one kept edge, and 2 (n - 1) or
+    4 (n - 1) more for a frame with n"""
+    u1, u4 = DC.oracle("one_edge")["units"], DC.oracle("pix:7,9,1.0")["units"]         # frame 3 of the 13 edges keeps four
+    print("\nunits:", u1)
+    assert u1 == DC.DOCUMENTED_UNITS, u1
+    twice = {"QB0", "v2", "v3", "v4", "v5", "v6"}
+    once = {"c", "b", "cpe", "Q", "bb", "QB1", "QB2"}
+    assert {k: u4[k] - u1[k] for k in u1} == {k: 12 if k in twice else 6 if k in once else 0 for k in u1}
+
+
+def _oracle_args(c, alpha=None):
+    return (c["tgt"], c["wgt"], c["eta"], c["poses"], c["disps"], c["intr"], c["ii"], c["jj"], c["mono"], c["scales"], c["shifts"],
+            c["vmask"], c["ignore_frames"], float(np.float32(c["lm"])), float(np.float32(c["ep"])),
+            c["alpha"] if alpha is None else alpha, 1, c["keep"])
+
+
+@pytest.mark.parametrize("name", ["pix:7,9,1.0", "pix:5,13,0.01", "dup", "oob:short_poses", "mask:u8", "singular", "stereo_only"])
+def test_linearize_mag_reproduces_the_dwq_and_dz_of_ba_with_scale_shift(name):
+    c, o = DC.case(name), DC.oracle(name)
+    sa = float(np.float32(np.sqrt(c["alpha"])))           # the kernel's sqrt_alpha is one fp32 rounding: the oracle gets its square
+    _, _, _, dwq, dz = D.ba_with_scale_shift(*_oracle_args(c, sa * sa))
+    mine = D.solve_rows(o)
+    np.testing.assert_allclose(mine, dwq, rtol=1e-9, atol=1e-9 * np.abs(dwq).max())
+    np.testing.assert_allclose(D.back_substitute(o, mine).v, dz, rtol=1e-9, atol=1e-9 * np.abs(dz).max())
+    assert np.abs(dz).max() > 1e-4
+
+
+@pytest.mark.parametrize("name", ["oob", "oob:long_poses", "oob:short_poses"])
+def test_oracle_with_out_of_range_edges_equals_the_oracle_on_the_filtered_list(name):
+    c = DC.case(name)
+    nv = min(len(c["poses"]), len(c["disps"]))
+    keep = R.kept_edges(c["ii"], c["jj"], nv)
+    a = list(_oracle_args(c))
+    b = list(a)
+    b[0], b[1], b[6], b[7] = c["tgt"][keep], c["wgt"][keep], [c["ii"][e] for e in keep], [c["jj"][e] for e in keep]
+    assert D.depth_frames(c["ii"], c["jj"], nv) == D.depth_frames(b[6]) and len(b[6]) < len(c["ii"])
+    for x, y in zip(D.ba_with_scale_shift(*a), D.ba_with_scale_shift(*b)):
+        np.testing.assert_array_equal(x, y)
+    step = lambda tg, wg, ii, jj: D.depth_scale_step(c["poses"], c["disps"], c["intr"], c["mono"], c["vmask"], c["scales"], c["shifts"],
+                                                     nv, tg, wg, c["eta"], ii, jj, itrs=1)
+    full, filt = step(c["tgt"], c["wgt"], c["ii"], c["jj"]), step(b[0], b[1], b[6], b[7])
+    for x, y in zip(full[:3], filt[:3]):
+        np.testing.assert_array_equal(x, y)
+    np.testing.assert_array_equal(full[3][keep], filt[3])
+    assert not full[3][[e for e in range(len(c["ii"])) if e not in keep]].any() and full[4] == filt[4]
