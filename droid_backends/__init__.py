@@ -19,6 +19,10 @@ The correlation lookups of the update operator (modules/droid_net/corr.py), back
     corr_index_backward(volume, coords, corr_grad, radius) -> [volume_grad]        (only the shape of volume is used)
     altcorr_forward(fmap1 [B,H1,W1,C], fmap2 [B,H2,W2,C], coords [B,N,H1,W1,2], radius) -> [corr [B,N,rd*rd,H1,W1]]      (fp32)
     altcorr_backward(fmap1, fmap2, coords, corr_grad, radius) -> [fmap1_grad, fmap2_grad, coords_grad]                   (fp32)
+    altcorr_pyramid_forward(levels, src [E], dst [E], coords [E,H,W,2], radius) -> [corr [E,len(levels)*rd*rd,H,W]]       (fp32 out)
+        levels: 1 to 4 maps [F, H >> l, W >> l, C], all fp16 or all fp32; src, dst int64 frame indices.  One launch: level l fills the
+        channels [l*rd*rd, (l+1)*rd*rd) with altcorr_forward(levels[0][src], levels[l][dst], coords / 2^l).  A level without pixels
+        and an edge with an index outside [0, F) give zeros; an edge gives the same bits alone and inside any batch; radius <= 4.
 
 Outputs run over the x offset first, then the y offset, as in the reference.  A sample is bilinear with zero padding, summed in fp32
 and rounded once.  A pixel whose floor(x0) or floor(y0) is not finite, or lies more than radius+2 outside the map, gives exact zeros
@@ -34,7 +38,7 @@ import torch
 from splat_slam_amd import _native as nat
 
 __all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "corr_index_forward", "corr_index_backward", "altcorr_forward",
-           "altcorr_backward"]
+           "altcorr_backward", "altcorr_pyramid_forward"]
 
 
 def _gpu(name, t, dtype, ndim=None):
@@ -305,3 +309,45 @@ def altcorr_backward(fmap1, fmap2, coords, corr_grad, radius):
                                                   fmap1_grad.data_ptr(), fmap2_grad.data_ptr(), B, N, H1, W1, H2, W2, C, radius,
                                                   _stream(dev)), "sgr_corr_alt_backward")
     return [fmap1_grad, fmap2_grad, coords_grad]
+
+
+def altcorr_pyramid_forward(levels, src, dst, coords, radius):
+    fn = "altcorr_pyramid_forward"
+    if not isinstance(levels, (list, tuple)) or not 1 <= len(levels) <= nat.SGR_CORR_PYRAMID_MAX_LEVELS:
+        raise ValueError(f"droid_backends.{fn}: levels must be a list of 1 to {nat.SGR_CORR_PYRAMID_MAX_LEVELS} tensors")
+    if not isinstance(levels[0], torch.Tensor):
+        raise TypeError("droid_backends: levels[0] must be a torch.Tensor")
+    dtype = levels[0].dtype
+    if dtype not in (torch.float16, torch.float32):
+        raise TypeError(f"droid_backends: levels must be torch.float16 or torch.float32, got {dtype}")
+    for l, m in enumerate(levels):
+        _gpu(f"levels[{l}]", m, dtype, 4)
+    F, H, W, C = levels[0].shape
+    for l, m in enumerate(levels):
+        if tuple(m.shape) != (F, H >> l, W >> l, C):
+            raise ValueError(f"droid_backends.{fn}: levels[{l}] must be [F, H >> {l}, W >> {l}, C] = {(F, H >> l, W >> l, C)}, "
+                             f"got {tuple(m.shape)}")
+    E = _edges(src, dst)
+    _gpu("coords", coords, torch.float32, 4)
+    if tuple(coords.shape) != (E, H, W, 2):
+        raise ValueError(f"droid_backends.{fn}: coords must be [E,H,W,2] = {(E, H, W, 2)}, got {tuple(coords.shape)}")
+    if C < 4 or C % 4:
+        raise ValueError(f"droid_backends.{fn}: the channel count must be a positive multiple of 4, got {C}")
+    radius = _radius(fn, radius)
+    if radius > nat.SGR_CORR_PYRAMID_MAX_RADIUS:
+        raise ValueError(f"droid_backends.{fn}: radius {radius} exceeds the supported {nat.SGR_CORR_PYRAMID_MAX_RADIUS}")
+    if F < 1 or H < 1 or W < 1:
+        raise ValueError(f"droid_backends.{fn}: levels[0] must be [F,H,W,C] with F, H, W > 0, got {tuple(levels[0].shape)}")
+    if E * H * W > _I32 or F > _I32:
+        raise ValueError(f"droid_backends.{fn}: E*H*W and F must each fit in int32")
+    dev = _same_device(*levels, src, dst, coords)
+    rd = 2 * radius + 1
+    corr = torch.empty((E, len(levels) * rd * rd, H, W), dtype=torch.float32, device=dev)
+    if E == 0:
+        return [corr]
+    ptrs = [m.data_ptr() if m.numel() else None for m in levels] + [None] * (nat.SGR_CORR_PYRAMID_MAX_LEVELS - len(levels))
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().sgr_corr_alt_pyramid_forward(*ptrs, src.data_ptr(), dst.data_ptr(), coords.data_ptr(), corr.data_ptr(),
+                                                         nat.SGR_CORR_F16 if dtype == torch.float16 else nat.SGR_CORR_F32, F, E, H, W, C,
+                                                         radius, len(levels), _stream(dev)), "sgr_corr_alt_pyramid_forward")
+    return [corr]

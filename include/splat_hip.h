@@ -769,6 +769,17 @@ int sgr_corr_alt_forward(const float* fmap1, const float* fmap2, const float* co
 int sgr_corr_alt_backward(const float* fmap1, const float* fmap2, const float* coords, const float* corr_grad, float* fmap1_grad,
                           float* fmap2_grad, int32_t batch, int32_t num, int32_t h1, int32_t w1, int32_t h2, int32_t w2, int32_t channels,
                           int32_t radius, void* stream);
+/* corr_alt_forward at every level of a feature pyramid in one launch, the two frames of an edge read through their indices.
+ * level_l [frames, h >> l, w >> l, channels], channels last, fp16 or fp32 by `dtype`, l < num_levels <= 4 (the others are ignored; a
+ * level without pixels may be NULL); src, dst [edges] int64; coords [edges,h,w,2] fp32 (x, y) at the scale of level 0;
+ * corr [edges, num_levels*rd*rd, h, w] fp32: level l fills the channels [l*rd*rd, (l+1)*rd*rd), x offset first, and is
+ * corr_alt_forward(level_0[src], level_l[dst], coords * 2^-l).  The window rule above applies per level; a level without pixels
+ * and an edge whose src or dst lies outside [0, frames) give zeros and read nothing.  Products and sums are fp32 (fp16 is widened
+ * exactly), one fixed chain per dot product: an edge gives the same bits alone and inside any batch.  edges*h*w must fit int32,
+ * channels is a positive multiple of 4, radius <= 4 (SGR_ERR_CAPACITY beyond). */
+int sgr_corr_alt_pyramid_forward(const void* level0, const void* level1, const void* level2, const void* level3, const int64_t* src,
+                                 const int64_t* dst, const float* coords, float* corr, int32_t dtype, int32_t frames, int32_t edges,
+                                 int32_t h, int32_t w, int32_t channels, int32_t radius, int32_t num_levels, void* stream);
 
 /* The factor graph of the tracker (FactorGraph, thirdparty/glorie_slam/factor_graph.py).  Stated in DESIGN.md section 3, "Factor
  * graph".  Everything is stream-ordered, allocates nothing, synchronises nothing and is bitwise reproducible.

@@ -199,6 +199,7 @@ SGR_CORR_F32, SGR_CORR_F16 = 0, 1
 SGR_VIDEO_MASK_F32, SGR_VIDEO_MASK_F16 = 0, 1
 SGR_VIDEO_MAX_FRAMES = 65535
 SGR_CORR_MAX_RADIUS = 1023
+SGR_CORR_PYRAMID_MAX_RADIUS, SGR_CORR_PYRAMID_MAX_LEVELS = 4, 4
 SGR_GRAPH_MAX_EDGES = 65535
 SGR_GRAPH_MAX_SIDE = 512
 
@@ -297,6 +298,7 @@ SIGNATURES = {
     "sgr_corr_index_backward": (C.c_int, [_fp, _fp, _fp] + [C.c_int32] * 7 + [_fp]),
     "sgr_corr_alt_forward": (C.c_int, [_fp, _fp, _fp, _fp] + [C.c_int32] * 8 + [_fp]),
     "sgr_corr_alt_backward": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp] + [C.c_int32] * 8 + [_fp]),
+    "sgr_corr_alt_pyramid_forward": (C.c_int, [_fp] * 8 + [C.c_int32] * 8 + [_fp]),
     "sgr_graph_reproject": (C.c_int, [_fp, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_int32, _fp, _fp, _fp, _fp,
                                       _fp]),
     "sgr_graph_select_scratch_bytes": (C.c_size_t, [C.c_int32] * 2),

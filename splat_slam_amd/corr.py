@@ -9,16 +9,21 @@ droid_backends already has (`sgr_corr_*`, csrc/sgr_corr.hip).  No kernel of its 
         keeps a pyramid of the maps instead of the volumes; block(coords [B,E,H,W,2], ii, jj) -> [B,E,num_levels*(2r+1)^2,H,W]
         correlates frame ii[e] at full resolution with frame jj[e] at every level (altcorr_forward, fp32).
         coords [B,E,H,W,S,2] gives [B,E,num_levels*(2r+1)^2,H,W,S].
+    FusedAltCorrBlock(fmaps [1,N,C,H,W], num_levels=4, radius=3)
+        the same pyramid, values and dtype, and the same call for coords [1,E,H,W,2]: one altcorr_pyramid_forward launch over every
+        level, reading frames ii[e] and jj[e] out of the pyramid through their indices (no gathered copies, no concatenation).  Both
+        classes define the same real-valued function; the fp32 sums differ in their order.  At most 4 levels, radius <= 4.
 
 A level whose map would have no pixel left (maps smaller than 2^level) is empty and its
-lookups are zeros.  Every tensor lives on the GPU.  Not provided: autograd through either block, a fused multi-level lookup.
+lookups are zeros.  Every tensor lives on the GPU.  Not provided: autograd through any block, a fused multi-level lookup of CorrBlock,
+the S dimension in FusedAltCorrBlock.
 """
 import torch
 import torch.nn.functional as F
 
 import droid_backends
 
-__all__ = ["CorrBlock", "AltCorrBlock"]
+__all__ = ["CorrBlock", "AltCorrBlock", "FusedAltCorrBlock"]
 
 
 def _halve(maps):
@@ -92,3 +97,28 @@ class AltCorrBlock:
         if squeeze:
             corr = corr.squeeze(-1)
         return corr.contiguous()
+
+
+class FusedAltCorrBlock:
+    def __init__(self, fmaps, num_levels=4, radius=3):
+        if fmaps.dim() != 5:
+            raise ValueError(f"FusedAltCorrBlock: fmaps must be [B,N,C,H,W], got {tuple(fmaps.shape)}")
+        if fmaps.shape[0] != 1:
+            raise ValueError(f"FusedAltCorrBlock: B must be 1, got fmaps {tuple(fmaps.shape)}")
+        self.num_levels, self.radius = int(num_levels), int(radius)
+        B, N, C, H, W = fmaps.shape
+        fmaps = fmaps.reshape(B * N, C, H, W) / 4.0
+        self.pyramid = []
+        for lvl in range(self.num_levels):
+            self.pyramid.append(fmaps.permute(0, 2, 3, 1).contiguous().view(B, N, H // 2 ** lvl, W // 2 ** lvl, C))
+            if lvl + 1 < self.num_levels:
+                fmaps = _halve(fmaps)
+
+    def __call__(self, coords, ii, jj):
+        if coords.dim() != 5:
+            raise ValueError(f"FusedAltCorrBlock: coords must be [1,E,H,W,2], got {tuple(coords.shape)}; AltCorrBlock takes [B,E,H,W,S,2]")
+        if coords.shape[0] != 1:
+            raise ValueError(f"FusedAltCorrBlock: B must be 1, got coords {tuple(coords.shape)}")
+        corr, = droid_backends.altcorr_pyramid_forward([maps[0] for maps in self.pyramid], ii.long().contiguous(), jj.long().contiguous(),
+                                                       coords[0].float().contiguous(), self.radius)
+        return corr[None]

@@ -4,6 +4,8 @@
 //   sgr_corr_index_backward  corr_index_backward: its transpose, every element of volume_grad written once
 //   sgr_corr_alt_forward     altcorr_forward: the same window with the correlations computed on the fly from two feature maps
 //   sgr_corr_alt_backward    altcorr_backward: gradients of that with respect to both feature maps
+//   sgr_corr_alt_pyramid_forward  altcorr_forward at every level of a feature pyramid in one launch, the frames of each edge read
+//                            through their indices out of an fp16 or fp32 store (the low-memory lookup of FactorGraph.update_lowmem)
 // Layout and measured times: DESIGN.md section 3, "Correlation lookups".  Outputs are indexed x offset first, then y offset.  Sums
 // are kept in fp32 registers and rounded once on the store; every output element is written exactly once.  Only fmap2_grad is a
 // scatter with collisions (fp32 global atomic adds, one 256-byte channel segment per wave instruction): everything else is owned
@@ -245,6 +247,115 @@ __global__ void __launch_bounds__(kThreads) altcorr_bwd_kernel(const float* __re
   }
 }
 
+// ---- altcorr over a pyramid: levels[l] [F,H>>l,W>>l,C] (fp16 or fp32), src, dst [E], coords [E,H,W,2], corr [E,L*rd*rd,H,W]
+constexpr int kMaxPyramidLevels = 4;
+constexpr size_t kPyramidLdsTarget = 32 * 1024;     // the output tile is halved until a workgroup needs no more than this
+
+struct PyramidLevels {
+  const void* map[kMaxPyramidLevels];
+};
+
+typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
+typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+
+// sum over the C channels of two rows as one chain of fused multiply-adds in channel order (fp16 widened in the instruction:
+// v_fma_mix_f32); a is the same address in every lane
+__device__ __forceinline__ float dot_rows(const float* __restrict__ a, const float* __restrict__ b, int C) {
+  float s = 0.f;
+#pragma unroll 4
+  for (int c = 0; c < C; c += 4) {
+    const float4 x = *(const float4*)(a + c), y = *(const float4*)(b + c);
+    s = fmaf(x.w, y.w, fmaf(x.z, y.z, fmaf(x.y, y.y, fmaf(x.x, y.x, s))));
+  }
+  return s;
+}
+__device__ __forceinline__ float dot_rows(const _Float16* __restrict__ a, const _Float16* __restrict__ b, int C) {
+  float s = 0.f;
+  if ((C & 7) == 0) {                                // rows are 16-byte aligned: one 16-byte load per lane and step
+#pragma unroll 4
+    for (int c = 0; c < C; c += 8) {
+      const half8_t x = *(const half8_t*)(a + c), y = *(const half8_t*)(b + c);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) s = fmaf((float)x[i], (float)y[i], s);
+    }
+  } else {
+    for (int c = 0; c < C; c += 4) {
+      const half4_t x = *(const half4_t*)(a + c), y = *(const half4_t*)(b + c);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) s = fmaf((float)x[i], (float)y[i], s);
+    }
+  }
+  return s;
+}
+
+// A workgroup owns `tile` consecutive pixels of one edge; its four waves take them in turn.  For one pixel the (level, corner)
+// pairs are dealt to the lanes, x-adjacent corners (contiguous rows of the level's map) to adjacent lanes: at r = 3 every level is
+// exactly one wave.  A lane walks the channels of its own row against the pixel's fmap1 row, whose address is the same in every lane
+// (scalar loads), so a dot product is one chain of fused multiply-adds in one lane: no reduction across lanes, and bits that depend
+// on the edge and the pixel alone.  The dots go to LDS, the L*rd*rd outputs are spread from them, and the tile's outputs leave
+// through LDS so that the store to each output plane is one run of `tile` consecutive pixels.
+template <typename T>
+__global__ void __launch_bounds__(kThreads) altcorr_pyramid_fwd_kernel(PyramidLevels lv, const int64_t* __restrict__ src,
+                                                                       const int64_t* __restrict__ dst,
+                                                                       const float* __restrict__ coords, float* __restrict__ corr,
+                                                                       int F, int H, int W, int C, int r, int L, int tile,
+                                                                       int tiles_per) {
+  extern __shared__ float lds[];
+  const int rd = 2 * r + 1, rc = rd + 1, nc = rc * rc, no = rd * rd, items = L * nc, outs = L * no, stride = tile + 1, HW = H * W;
+  float* outt = lds;                                   // [outs][tile + 1]
+  float* dots = lds + (size_t)outs * stride;           // [kWaves][items], corner (ix, iy) of level l at l * nc + iy * rc + ix
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int e = blockIdx.x / tiles_per, t0 = (blockIdx.x - e * tiles_per) * tile;
+  const int64_t fs = src[e], fd = dst[e];
+  const bool edge_in = fs >= 0 && fs < F && fd >= 0 && fd < F;       // as sgr_graph_reproject: zeros, and nothing is read
+  const int npx = min(tile, HW - t0);
+  float* mydots = dots + wave * items;
+  for (int px0 = 0; px0 < npx; px0 += kWaves) {        // uniform trip count: the barriers below are taken by every wave
+    const int px = px0 + wave;
+    const bool active = px < npx;
+    float x0 = 0.f, y0 = 0.f;
+    if (active) {
+      const int yx = t0 + px;
+      const float* cp = coords + ((int64_t)e * HW + yx) * 2;
+      x0 = cp[0];
+      y0 = cp[1];
+      const T* f1 = (const T*)lv.map[0] + (edge_in ? ((int64_t)fs * HW + yx) * C : 0);
+      for (int item = lane; item < items; item += 64) {
+        const int l = item / nc, k = item - l * nc, iy = k / rc, ix = k - iy * rc;
+        const int Hl = H >> l, Wl = W >> l;
+        const float scale = 1.f / (float)(1 << l);     // a power of two: coords * scale == coords / 2^l exactly
+        const Window w = make_window(x0 * scale, y0 * scale, r, Hl, Wl);
+        const int x2 = w.fx - r + ix, y2 = w.fy - r + iy;
+        float s = 0.f;
+        if (edge_in && w.live && x2 >= 0 && x2 < Wl && y2 >= 0 && y2 < Hl) {
+          const void* base = l == 0 ? lv.map[0] : l == 1 ? lv.map[1] : l == 2 ? lv.map[2] : lv.map[3];
+          s = dot_rows(f1, (const T*)base + (((int64_t)fd * Hl + y2) * Wl + x2) * C, C);
+        }
+        mydots[item] = s;
+      }
+    }
+    __syncthreads();
+    if (active) {
+      for (int o = lane; o < outs; o += 64) {
+        const int l = o / no, q = o - l * no, ax = q / rd, ay = q - ax * rd;
+        const int Hl = H >> l, Wl = W >> l;
+        const float scale = 1.f / (float)(1 << l);
+        const Window w = make_window(x0 * scale, y0 * scale, r, Hl, Wl);
+        const float wx0 = 1.f - w.dx, wy0 = 1.f - w.dy;
+        const float* d = mydots + l * nc + ay * rc + ax;
+        const bool on = edge_in && w.live && Hl > 0 && Wl > 0;
+        outt[o * stride + px] = on ? wy0 * (wx0 * d[0] + w.dx * d[1]) + w.dy * (wx0 * d[rc] + w.dx * d[rc + 1]) : 0.f;
+      }
+    }
+    __syncthreads();
+  }
+  float* out = corr + (int64_t)e * outs * HW + t0;
+  for (int i = threadIdx.x; i < outs * tile; i += kThreads) {
+    const int o = i / tile, px = i - o * tile;
+    if (px < npx) out[(int64_t)o * HW + px] = outt[o * stride + px];
+  }
+}
+
 inline bool fits_i32(int64_t v) { return v >= 0 && v <= INT32_MAX; }
 
 template <typename T>
@@ -335,6 +446,39 @@ int sgr_corr_alt_forward(const float* fmap1, const float* fmap2, const float* co
   hipLaunchKernelGGL(altcorr_fwd_kernel, dim3((unsigned)nblocks), dim3(kThreads), lds_bytes(tile), (hipStream_t)stream, fmap1, fmap2, coords,
                      corr, num, HW1, h2, w2, channels / 4, radius, tile, tiles_per);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "corr_alt_forward launch failed");
+}
+
+int sgr_corr_alt_pyramid_forward(const void* level0, const void* level1, const void* level2, const void* level3, const int64_t* src,
+                                 const int64_t* dst, const float* coords, float* corr, int32_t dtype, int32_t frames, int32_t edges,
+                                 int32_t h, int32_t w, int32_t channels, int32_t radius, int32_t num_levels, void* stream) {
+  const char* what = "corr_alt_pyramid_forward";
+  if (!src || !dst || !coords || !corr) return set_error(SGR_ERR_INVALID, "%s: null argument", what);
+  if (dtype != SGR_CORR_F32 && dtype != SGR_CORR_F16) return set_error(SGR_ERR_INVALID, "%s: dtype must be SGR_CORR_F32 or SGR_CORR_F16", what);
+  if (num_levels < 1 || num_levels > kMaxPyramidLevels)
+    return set_error(SGR_ERR_INVALID, "%s: num_levels (%d) must lie in [1, %d]", what, num_levels, kMaxPyramidLevels);
+  if (frames < 1) return set_error(SGR_ERR_INVALID, "%s: frames (%d) must be positive", what, frames);
+  if (int rc = alt_sizes(what, 1, edges, h, w, h, w, channels, radius)) return rc;
+  if (radius > kMaxRegRadius) return set_error(SGR_ERR_CAPACITY, "%s: radius %d exceeds the supported %d", what, radius, kMaxRegRadius);
+  PyramidLevels lv = {{level0, level1, level2, level3}};
+  for (int l = 0; l < kMaxPyramidLevels; ++l) {
+    if (l >= num_levels) lv.map[l] = nullptr;
+    else if (!lv.map[l] && (h >> l) > 0 && (w >> l) > 0) return set_error(SGR_ERR_INVALID, "%s: level %d is null", what, l);
+  }
+  const int rd = 2 * radius + 1, HW = h * w, outs = num_levels * rd * rd, items = num_levels * (rd + 1) * (rd + 1);
+  auto lds_bytes = [&](int tile) { return ((size_t)outs * (tile + 1) + (size_t)kWaves * items) * sizeof(float); };
+  int tile = kAltTile;
+  while (tile > 1 && lds_bytes(tile) > kPyramidLdsTarget) tile >>= 1;
+  const int tiles_per = (HW + tile - 1) / tile;
+  const int64_t nblocks = (int64_t)edges * tiles_per;
+  if (!fits_i32(nblocks)) return set_error(SGR_ERR_CAPACITY, "%s: too many pixels", what);
+  const dim3 grid((unsigned)nblocks), block(kThreads);
+  if (dtype == SGR_CORR_F16)
+    hipLaunchKernelGGL((altcorr_pyramid_fwd_kernel<_Float16>), grid, block, lds_bytes(tile), (hipStream_t)stream, lv, src, dst, coords, corr,
+                       frames, h, w, channels, radius, num_levels, tile, tiles_per);
+  else
+    hipLaunchKernelGGL((altcorr_pyramid_fwd_kernel<float>), grid, block, lds_bytes(tile), (hipStream_t)stream, lv, src, dst, coords, corr,
+                       frames, h, w, channels, radius, num_levels, tile, tiles_per);
+  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "%s launch failed", what);
 }
 
 int sgr_corr_alt_backward(const float* fmap1, const float* fmap2, const float* coords, const float* corr_grad, float* fmap1_grad,

@@ -20,7 +20,7 @@ stream-ordered.  The matrix is at most 512 x 512 (the DepthVideo buffer limit). 
 import torch
 
 from splat_slam_amd import _native as nat
-from splat_slam_amd.corr import AltCorrBlock, CorrBlock
+from splat_slam_amd.corr import AltCorrBlock, CorrBlock, FusedAltCorrBlock
 
 __all__ = ["reproject", "select_proximity_edges", "select_backend_edges", "FactorGraph"]
 
@@ -183,6 +183,8 @@ class FactorGraph:
     `add_factors, rm_factors, rm_keyframe, filter_edges, clear_edges, update, update_lowmem, add_neighborhood_factors,
     add_proximity_factors, add_backend_proximity_factors`.  `update_op(net, inp, corr, motn, ii, jj) -> (net, delta, weight, damping,
     upmask)` is any callable with the signature of the reference's update operator; the graph does not contain the network.
+    `corr_impl`: "volume" keeps a CorrBlock per edge (the frontend); "alt" and "alt_fused" keep none and differ only in the
+    operator `update_lowmem` builds (AltCorrBlock, FusedAltCorrBlock).
 
     New edges that are already active or inactive are dropped, on the device (keys i * 2^31 + j, torch.isin).
 
@@ -322,9 +324,11 @@ class FactorGraph:
 
     @torch.no_grad()
     def update_lowmem(self, t0=None, t1=None, itrs=2, use_inactive=False, EP=1e-7, steps=8, enable_wq=True):
-        """`steps` passes with the low-memory correlation operator, the edges taken in chunks of 8 source frames"""
+        """`steps` passes with the low-memory correlation operator (corr_impl "alt_fused": FusedAltCorrBlock, one launch per chunk;
+        otherwise AltCorrBlock), the edges taken in chunks of 8 source frames"""
         num, rig, ch, ht, wd = self.video.fmaps.shape
-        corr_op = AltCorrBlock(self.video.fmaps.view(1, num * rig, ch, ht, wd))
+        block = FusedAltCorrBlock if self.corr_impl == "alt_fused" else AltCorrBlock
+        corr_op = block(self.video.fmaps.view(1, num * rig, ch, ht, wd))
         for step in range(steps):
             coords1, motn = self._motion()
             for first in range(0, int(self.jj.max()) + 1, 8):
