@@ -749,6 +749,32 @@ int sgr_video_valid_mask(const float* poses, const float* disps, int32_t num_fra
                          const int64_t* inds, int32_t num, float rel, int32_t visible_num, uint8_t* mask_out, void* scratch,
                          size_t scratch_bytes, void* stream);
 
+/* Keyframe depth fusion: the depth map the mapper seeds and supervises with (Mapper.get_w2c_and_depth, src/mapper.py:258-301).  Stated
+ * in DESIGN.md section 3, "Keyframe depth fusion".  Everything is stream-ordered, allocates nothing, synchronises nothing and is
+ * bitwise reproducible (fixed-order sums, no floating-point atomics).  ht, wd >= 1, ht * wd < 2^28, num <= 65535.
+ * sgr_fuse_prepare: for each of `num` mono-depth maps [num, ht, wd] (what depends on the mono map alone; once per keyframe):
+ *   mean = sum / (ht wd), the sum in fp64 in the order of sgr_video_depth_thresh, rounded once; pixels > 4 mean become 0;
+ *   eroded [num, ht, wd] bytes = 1 iff every pixel within chessboard distance 5 inside the image is > 0 (outside counts as > 0);
+ *   mono_filled [num, ht, wd] = the map where eroded == 1; the others are filled in passes k = 1, 2, ...: with K the set known
+ *   before pass k (K = eroded at first), every pixel outside K with an 8-neighbour in K gets sum w v / sum w over the pixels of K in
+ *   its 7 x 7 window, w = 1 / (dx^2 + dy^2), fp32, row-major; the pixels filled in a pass join K after it.  A map without a known
+ *   pixel stays zero.
+ * sgr_fuse_depth: for each of `num` frames f = inds[b] (int64, any order, repeats allowed), read in place from disps_up,
+ *   valid_depth_mask (bytes, non-zero = valid), mono_filled and eroded, all [num_frames, ht, wd]:
+ *   count = sum valid; invalid[b] = count < min_valid; (s, q) = the scale and shift of sgr_dspo_align with prediction mono_filled,
+ *   target 1.0f / disp and weight eroded & valid (sums and the 2 x 2 solve in fp64, rounded once; pixels of weight zero contribute
+ *   nothing; a zero determinant gives IEEE inf / NaN); depth [num, ht, wd] = valid ? 1.0f / disp : s * mono_filled + q, a rounded
+ *   multiply followed by a rounded add; scale[b] = s, shift[b] = q.  An invalid frame gets depth = valid ? 1.0f / disp : 0 and its
+ *   scale and shift are left unwritten.  A slot whose index lies outside [0, num_frames) gets invalid = 1 and a depth of zeros.  A frame
+ *   gives the same bits alone and in any batch.
+ * scratch: sgr_fuse_scratch_bytes(num, ht, wd) bytes, 16-byte aligned, serves either call (0 = unsupported sizes). */
+size_t sgr_fuse_scratch_bytes(int32_t num, int32_t ht, int32_t wd);
+int sgr_fuse_prepare(const float* mono, int32_t num, int32_t ht, int32_t wd, float* mono_filled, uint8_t* eroded, void* scratch,
+                     size_t scratch_bytes, void* stream);
+int sgr_fuse_depth(const float* disps_up, const uint8_t* valid_depth_mask, const float* mono_filled, const uint8_t* eroded,
+                   int32_t num_frames, int32_t ht, int32_t wd, const int64_t* inds, int32_t num, int32_t min_valid, float* depth,
+                   float* scale, float* shift, uint8_t* invalid, void* scratch, size_t scratch_bytes, void* stream);
+
 /* Correlation lookups of the tracker's update operator (droid_backends).  rd = 2*radius + 1; outputs run over the x offset first,
  * then the y offset.  A sample is bilinear with zero padding; a pixel whose floor(x0) or floor(y0) is not finite or lies outside
  * [-(radius+2), w2+radius+1] resp. [-(radius+2), h2+radius+1] reads nothing and gives zeros (no coordinate value reaches memory).

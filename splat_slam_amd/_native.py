@@ -198,6 +198,7 @@ SGR_DSPO_WEIGHTS_NONE, SGR_DSPO_WEIGHTS_F32, SGR_DSPO_WEIGHTS_U8 = 0, 1, 2
 SGR_CORR_F32, SGR_CORR_F16 = 0, 1
 SGR_VIDEO_MASK_F32, SGR_VIDEO_MASK_F16 = 0, 1
 SGR_VIDEO_MAX_FRAMES = 65535
+SGR_FUSE_MAX_FRAMES = 65535
 SGR_CORR_MAX_RADIUS = 1023
 SGR_CORR_PYRAMID_MAX_RADIUS, SGR_CORR_PYRAMID_MAX_LEVELS = 4, 4
 SGR_GRAPH_MAX_EDGES = 65535
@@ -294,6 +295,10 @@ SIGNATURES = {
                                              _fp]),
     "sgr_video_valid_mask": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, C.c_int32, C.c_float, C.c_int32, _fp, _fp,
                                        C.c_size_t, _fp]),
+    "sgr_fuse_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "sgr_fuse_prepare": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_size_t, _fp]),
+    "sgr_fuse_depth": (C.c_int, [_fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp,
+                                 C.c_size_t, _fp]),
     "sgr_corr_index_forward": (C.c_int, [_fp, _fp, _fp] + [C.c_int32] * 7 + [_fp]),
     "sgr_corr_index_backward": (C.c_int, [_fp, _fp, _fp] + [C.c_int32] * 7 + [_fp]),
     "sgr_corr_alt_forward": (C.c_int, [_fp, _fp, _fp, _fp] + [C.c_int32] * 8 + [_fp]),

@@ -17,7 +17,8 @@ from splat_slam_amd.losses import get_median_depth
 class MappingSession:
     def __init__(self, loop, intr, pose_source=None):
         """loop: MappingLoop or FusedMappingLoop.  intr: dict W,H,fx,fy,cx,cy.
-        pose_source(video_idx) -> (w2c[4,4], depth[H,W]) or None: the tracker's refined estimate for a past keyframe."""
+        pose_source(video_idx) -> (w2c[4,4], depth[H,W]) or (w2c, depth, invalid) or None: the tracker's refined estimate for a past
+        keyframe; see refresh_keyframes."""
         self.loop = loop
         self.config = loop.config
         self.device = loop.device
@@ -95,6 +96,53 @@ class MappingSession:
         cam.update_RT(cam.R_gt, cam.T_gt)                 # mapper.py:939: the tracked pose becomes the camera pose
         return cam
 
+    def register_invalid(self, video_idx, idx, color, depth, w2c):
+        """A tracker keyframe with too few valid depth pixels (mapper.py:910-926): its camera is kept, so that later pose updates
+        reach it, but it is no mapping keyframe and nothing is rendered or optimised."""
+        self.keyframe_idxs.append(idx)
+        self.video_idxs.append(video_idx)
+        depth = torch.as_tensor(depth, dtype=torch.float32, device=self.device)
+        self.cameras[video_idx] = self._camera(video_idx, color, depth, w2c)
+        self.is_kf[video_idx] = False
+
+    def refresh_keyframes(self, skip_idx=None):
+        """Pose and depth of every registered keyframe from the pose source, and the deformation of the Gaussians anchored to the ones
+        that moved (mapper.py:1021-1055; with skip_idx None the final update of final_refine, :620-647).  The frame whose frame index
+        is skip_idx only has its first depth recorded.  A pose source with a `prefetch(video_idxs)` method is told once, before the
+        loop, which keyframes are about to be asked for; a third element `invalid` of its answer selects the rigid correction and
+        leaves the frame's reference depth alone (:1050-1055)."""
+        if self.pose_source is None:
+            return
+        loop = self.loop
+        prefetch = getattr(self.pose_source, "prefetch", None)
+        if prefetch is not None:
+            prefetch(list(self.video_idxs))
+        for keyframe_idx, frame_idx in zip(self.video_idxs, self.keyframe_idxs):
+            upd = self.pose_source(keyframe_idx)
+            if upd is None:
+                continue
+            w2c_temp, depth_temp = upd[0], upd[1]
+            invalid = len(upd) > 2 and bool(upd[2])
+            w2c_temp = w2c_temp.to(self.device)
+            depth_temp = torch.as_tensor(depth_temp, dtype=torch.float32, device=self.device)
+            if keyframe_idx not in self.depth_dict and self.is_kf.get(keyframe_idx, False):
+                self.depth_dict[keyframe_idx] = depth_temp
+            if skip_idx is not None and frame_idx == skip_idx:
+                continue
+            cam = self.cameras[keyframe_idx]
+            w2c_old = torch.eye(4, device=self.device)
+            w2c_old[:3, :3], w2c_old[:3, 3] = cam.R, cam.T
+            cam.update_RT(w2c_temp[:3, :3], w2c_temp[:3, 3])
+            cam.depth = depth_temp
+            if self.move_points and self.is_kf.get(keyframe_idx, False):
+                if invalid:
+                    update_mapping_points(loop.gaussians, keyframe_idx, w2c_temp, w2c_old, depth_temp, self.depth_dict[keyframe_idx],
+                                          self.intrinsics, method="rigid")
+                else:
+                    update_mapping_points(loop.gaussians, keyframe_idx, w2c_temp, w2c_old, depth_temp, self.depth_dict[keyframe_idx],
+                                          self.intrinsics)
+                    self.depth_dict[keyframe_idx] = depth_temp
+
     def process(self, video_idx, idx, color, depth, w2c):
         """One tracker message.  Returns "init", "mapped" or "skipped" (not a keyframe)."""
         loop = self.loop
@@ -129,28 +177,7 @@ class MappingSession:
         loop.current_window, _ = self.add_to_window(video_idx, curr_visibility, loop.occ_aware_visibility, loop.current_window)
         self.is_kf[video_idx] = True
         # past keyframes the tracker moved since they were mapped: deform the Gaussians anchored to them
-        last_idx = self.keyframe_idxs[-1]
-        if self.pose_source is not None:
-            for keyframe_idx, frame_idx in zip(self.video_idxs, self.keyframe_idxs):
-                upd = self.pose_source(keyframe_idx)
-                if upd is None:
-                    continue
-                w2c_temp, depth_temp = upd
-                w2c_temp = w2c_temp.to(self.device)
-                depth_temp = torch.as_tensor(depth_temp, dtype=torch.float32, device=self.device)
-                if keyframe_idx not in self.depth_dict and self.is_kf.get(keyframe_idx, False):
-                    self.depth_dict[keyframe_idx] = depth_temp
-                if frame_idx == last_idx:
-                    continue
-                cam = self.cameras[keyframe_idx]
-                w2c_old = torch.eye(4, device=self.device)
-                w2c_old[:3, :3], w2c_old[:3, 3] = cam.R, cam.T
-                cam.update_RT(w2c_temp[:3, :3], w2c_temp[:3, 3])
-                cam.depth = depth_temp
-                if self.move_points and self.is_kf.get(keyframe_idx, False):
-                    update_mapping_points(loop.gaussians, keyframe_idx, w2c_temp, w2c_old, depth_temp,
-                                          self.depth_dict[keyframe_idx], self.intrinsics)
-                    self.depth_dict[keyframe_idx] = depth_temp
+        self.refresh_keyframes(skip_idx=self.keyframe_idxs[-1])
         loop.viewpoints[video_idx] = viewpoint
         loop.add_next_kf(video_idx, viewpoint, depth_map=depth, init=False)
         loop.build_keyframe_optimizers()

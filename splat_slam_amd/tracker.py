@@ -6,6 +6,7 @@ DESIGN.md section 3, "Tracker".
         cfg: the reference's dict, read at cfg["device"], cfg["tracking"]["motion_filter"]["thresh"],
         cfg["tracking"]["frontend"][window, enable_online_ba], cfg["tracking"]["backend"]["ba_freq"], cfg["mapping"]["every_keyframe"]
         (and what Frontend and Backend read); net: a DroidNet; video: a DepthVideo.  Attributes: motion_filter, frontend, online_ba.
+        One more keyword, mono_depth=None: the mono-depth callable that is passed on to MotionFilter.
     tracker.run(stream)
         stream: len(stream), stream[i] -> (timestamp, image [1,3,H,W] in [0, 1], ...), stream.get_intrinsic() -> [4].
         Per frame: motion_filter.track(timestamp, image, intrinsic), then frontend().  When the index of the newest keyframe has
@@ -26,12 +27,13 @@ __all__ = ["Tracker"]
 
 
 class Tracker:
-    def __init__(self, cfg, net, video, on_keyframe=None, only_tracking=False):
+    def __init__(self, cfg, net, video, on_keyframe=None, only_tracking=False, mono_depth=None):
         self.cfg, self.net, self.video, self.device = cfg, net, video, cfg["device"]
         self.on_keyframe, self.only_tracking = on_keyframe, only_tracking
         tr = cfg["tracking"]
         self.frontend_window = tr["frontend"]["window"]
-        self.motion_filter = MotionFilter(net, video, thresh=tr["motion_filter"]["thresh"], device=self.device)
+        prior = {} if mono_depth is None else {"mono_depth": mono_depth}     # without one the filter is built exactly as before
+        self.motion_filter = MotionFilter(net, video, thresh=tr["motion_filter"]["thresh"], device=self.device, **prior)
         self.enable_online_ba = tr["frontend"]["enable_online_ba"]
         self.every_kf = cfg["mapping"]["every_keyframe"]
         self.frontend = Frontend(net, video, cfg)
