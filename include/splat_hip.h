@@ -983,6 +983,82 @@ int sgr_encoder_pack(const SgrUpdateTensor* src, int32_t n, int32_t H, int32_t W
 int sgr_encoder_conv(const SgrEncoderConv* conv, void* stream);
 int sgr_encoder_forward(const SgrEncoderWeights* weights, const SgrEncoderCall* call, void* scratch, size_t scratch_bytes, void* stream);
 
+/* The vision transformer of the mono-depth prior (timm's ViT blocks as the DPT of thirdparty/mono_priors/omnidata/modules/midas reads
+ * them), inference only.  Stated in DESIGN.md section 3, "Vision transformer".  Everything is stream-ordered, allocates nothing,
+ * synchronises nothing and is bitwise reproducible (no atomics; the order of every sum follows from the shape alone), and an image
+ * gives the same bits alone and inside any batch.  dim D = 64 * heads, heads 1..16, head dimension 64, hidden width 4 D, tokens
+ * T = 1 + gh * gw >= 2 per image, B * T must fit int32.  The residual stream is fp32 [B*T][D]; every GEMM operand is fp16, every sum
+ * fp32 (mfma_f32_16x16x32_f16).  fp16 buffers need 16-byte aligned bases and row strides that are multiples of 8 elements.
+ * sgr_vit_layernorm: out[m][:] = fp16((x[m][:] - mean) * rsqrt(var + 1e-6) * gamma + beta), biased variance, mean and variance in
+ * fp32 of the row shifted by its first element (a constant row gives beta exactly); x fp32 [M][D], D a multiple of 64 up to 1024.
+ * sgr_vit_gemm: v[m][n] = sum_k a[m * lda + k] w[n * ldw + k] + bias[n] (bias NULL: 0), M >= 1, N and K multiples of 64, then by epi:
+ *   STORE_F16  out fp16 [m * ldo + n] = v;   STORE_F32  out fp32 [m * ldo + n] = v;   GELU_F16  out fp16 [m * ldo + n] = gelu(v), the
+ *   exact erf form;   RESIDUAL  out fp32 [m * ldo + n] += v and, with tap, tap fp16 [m * ldo + n] = the updated value;
+ *   READOUT  row m = (image b, token t) of T tokens: t = 0 writes nothing, t > 0 writes out fp16 [(b * N + n) * (T - 1) + t - 1] =
+ *   gelu(v + aux[b * N + n]);   EMBED  row m = (image b, patch p) of T - 1 patches: out fp32 [(b * T + 1 + p) * ldo + n] =
+ *   v + aux[(1 + p) * N + n].
+ * sgr_vit_attention: qkv fp16 [B][T][3][heads][64] -> out fp16 [B][T][heads * 64] = softmax(q k^T / 8) v per (image, head), flash
+ * style: scores, running maximum and sum in fp32, the probabilities rounded to fp16 for the second product, one division at the end.
+ * sgr_vit_forward: patches fp16 [B][gh*gw][cin] (cin a multiple of 64) -> two tap maps fp16 [B][D][gh][gw].  pos is fp32 [T][D], row 0
+ * the class token plus its position row, row 1 + p the position row of patch p.  Launch 0 writes the stream (class rows, then the
+ * patch embedding with epilogue EMBED); block i is launches 1 + 7 i .. 7 + 7 i: norm1, qkv, attention, proj (RESIDUAL), norm2, fc1
+ * (GELU), fc2 (RESIDUAL, with the tap copy when i is tap[0] or tap[1]: the block's output before any final norm); then per tap j the
+ * class-token half of the readout, readout_w[j][:, D:] x_cls + readout_b[j] as fp32 [B][D], and the token half with epilogue READOUT:
+ * 5 + 7 depth launches, of which first_launch <= i <= last_launch are enqueued.  readout_w[j] is fp16 [D][2 D].
+ * scratch: sgr_vit_scratch_bytes(B, T, heads, depth) bytes, 16-byte aligned (0 = unsupported sizes). */
+#define SGR_VIT_EPI_STORE_F16 1
+#define SGR_VIT_EPI_GELU_F16 2
+#define SGR_VIT_EPI_RESIDUAL 3
+#define SGR_VIT_EPI_READOUT 4
+#define SGR_VIT_EPI_EMBED 5
+#define SGR_VIT_EPI_STORE_F32 6
+typedef struct SgrVitGemm {
+  const void* a;                   /* fp16 [M][lda] */
+  const void* w;                   /* fp16 [N][ldw] */
+  const float* bias;               /* [N] or NULL */
+  int64_t lda, ldw, ldo;
+  int32_t M, N, K, epi;
+  void* out;
+  void* tap;                       /* RESIDUAL: fp16 [M][ldo] or NULL */
+  const float* aux;                /* READOUT: [B][N]; EMBED: [T][N] */
+  int32_t T;                       /* READOUT, EMBED: tokens per image */
+} SgrVitGemm;
+typedef struct SgrVitBlock {
+  const float* ln1_g;
+  const float* ln1_b;
+  const void* qkv_w;               /* fp16 [3 D][D] */
+  const float* qkv_b;
+  const void* proj_w;              /* fp16 [D][D] */
+  const float* proj_b;
+  const float* ln2_g;
+  const float* ln2_b;
+  const void* fc1_w;               /* fp16 [4 D][D] */
+  const float* fc1_b;
+  const void* fc2_w;               /* fp16 [D][4 D] */
+  const float* fc2_b;
+} SgrVitBlock;
+typedef struct SgrVitWeights {
+  int32_t dim, heads, depth, cin;
+  int32_t tap[2];                  /* two distinct blocks in [0, depth) */
+  const void* embed_w;             /* fp16 [D][cin] */
+  const float* embed_b;
+  const SgrVitBlock* blocks;       /* host array [depth] */
+  const void* readout_w[2];
+  const float* readout_b[2];
+} SgrVitWeights;
+typedef struct SgrVitCall {
+  const void* patches;
+  int32_t B, gh, gw;
+  const float* pos;
+  void* out[2];
+  int32_t first_launch, last_launch;
+} SgrVitCall;
+size_t sgr_vit_scratch_bytes(int32_t B, int32_t T, int32_t heads, int32_t depth);
+int sgr_vit_layernorm(const float* x, const float* gamma, const float* beta, int64_t M, int32_t D, void* out, void* stream);
+int sgr_vit_gemm(const SgrVitGemm* gemm, void* stream);
+int sgr_vit_attention(const void* qkv, int32_t B, int32_t T, int32_t heads, void* out, void* stream);
+int sgr_vit_forward(const SgrVitWeights* weights, const SgrVitCall* call, void* scratch, size_t scratch_bytes, void* stream);
+
 /* SE3 ops, batched over n.  Pose =(tx,ty,tz,qx,qy,qz,qw) as in lietorch / depth_video.py:69; tau = (rho, theta). */
 int se3_exp(const float* tau, int64_t n, float* pose_out, void* stream);
 int se3_log(const float* pose, int64_t n, float* tau_out, void* stream);

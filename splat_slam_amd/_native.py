@@ -187,6 +187,27 @@ class SgrEncoderCall(C.Structure):
                 ("first_launch", C.c_int32), ("last_launch", C.c_int32)]
 
 
+class SgrVitGemm(C.Structure):
+    _fields_ = [("a", _fp), ("w", _fp), ("bias", _fp), ("lda", C.c_int64), ("ldw", C.c_int64), ("ldo", C.c_int64), ("M", C.c_int32),
+                ("N", C.c_int32), ("K", C.c_int32), ("epi", C.c_int32), ("out", _fp), ("tap", _fp), ("aux", _fp), ("T", C.c_int32)]
+
+
+class SgrVitBlock(C.Structure):
+    _fields_ = [(n, _fp) for n in ("ln1_g", "ln1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ln2_g", "ln2_b", "fc1_w", "fc1_b", "fc2_w",
+                                   "fc2_b")]
+
+
+class SgrVitWeights(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("heads", C.c_int32), ("depth", C.c_int32), ("cin", C.c_int32), ("tap", C.c_int32 * 2),
+                ("embed_w", _fp), ("embed_b", _fp), ("blocks", C.POINTER(SgrVitBlock)), ("readout_w", _fp * 2), ("readout_b", _fp * 2)]
+
+
+class SgrVitCall(C.Structure):
+    _fields_ = [("patches", _fp), ("B", C.c_int32), ("gh", C.c_int32), ("gw", C.c_int32), ("pos", _fp), ("out", _fp * 2),
+                ("first_launch", C.c_int32), ("last_launch", C.c_int32)]
+
+
+SGR_VIT_EPI = {"store_f16": 1, "gelu_f16": 2, "residual": 3, "readout": 4, "embed": 5, "store_f32": 6}
 SGR_ENCODER_NORM_NONE, SGR_ENCODER_NORM_INSTANCE = 0, 1
 SGR_ENCODER_ACTS = {"none": 0, "relu": 1, "split": 2}
 SGR_UPDATE_OUT_CL_F16, SGR_UPDATE_OUT_CL_F32 = 0, 1
@@ -318,6 +339,11 @@ SIGNATURES = {
     "sgr_encoder_pack": (C.c_int, [C.POINTER(SgrUpdateTensor)] + [C.c_int32] * 3 + [C.POINTER(C.c_float), C.POINTER(C.c_float), _fp, _fp]),
     "sgr_encoder_conv": (C.c_int, [C.POINTER(SgrEncoderConv), _fp]),
     "sgr_encoder_forward": (C.c_int, [C.POINTER(SgrEncoderWeights), C.POINTER(SgrEncoderCall), _fp, C.c_size_t, _fp]),
+    "sgr_vit_scratch_bytes": (C.c_size_t, [C.c_int32] * 4),
+    "sgr_vit_layernorm": (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int32, _fp, _fp]),
+    "sgr_vit_gemm": (C.c_int, [C.POINTER(SgrVitGemm), _fp]),
+    "sgr_vit_attention": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]),
+    "sgr_vit_forward": (C.c_int, [C.POINTER(SgrVitWeights), C.POINTER(SgrVitCall), _fp, C.c_size_t, _fp]),
     "se3_exp": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_log": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_inv": (C.c_int, [_fp, C.c_int64, _fp, _fp]),

@@ -13,8 +13,8 @@ goes up by one.  The nine items appended are the reference's: (tstamp, image[0],
 inp); the context maps are encoded only for frames that are appended.  One difference: the reference's first-frame branch passes
 `net[0, 0]`, which after its squeeze is a single channel plane that the video broadcasts over all 128 channels; here both branches store
 the whole [128,h,w] maps, as its later-frame branch does.  The single host synchronisation is the `.item()` of the decision, as in the
-reference.  This project builds neither a mono-depth network nor a dataset loader: with mono_depth None no prior is appended and
-video.mono_disps keeps its zeros.
+reference.  splat_slam_amd.mono_depth.MonoDepth is such a mono_depth callable; this project builds no dataset loader.  With mono_depth
+None no prior is appended and video.mono_disps keeps its zeros.
 """
 import torch
 

@@ -17,7 +17,8 @@ section 3, "Slam".
 On a keyframe: its mono map goes into the depth cache (prepared once), KeyframeDepth.get fuses it with the video's current state, and
 the result goes to session.process -- or, with fewer than 100 valid tracker pixels, the camera is registered as no mapping keyframe
 (mapper.py:910-926).  When a keyframe is mapped, the session asks for the current pose and depth of all past keyframes: they come from
-one batched fusion call (the pose source's prefetch).  Not provided: dataset loaders, a mono-depth network, trajectory scoring, logging.
+one batched fusion call (the pose source's prefetch).  The mono-depth network is splat_slam_amd.mono_depth.MonoDepth, itself such a callable.  Not provided: dataset loaders, trajectory
+scoring, logging.
 """
 import torch
 
