@@ -1059,7 +1059,91 @@ int sgr_vit_gemm(const SgrVitGemm* gemm, void* stream);
 int sgr_vit_attention(const void* qkv, int32_t B, int32_t T, int32_t heads, void* out, void* stream);
 int sgr_vit_forward(const SgrVitWeights* weights, const SgrVitCall* call, void* scratch, size_t scratch_bytes, void* stream);
 
-/* SE3 ops, batched over n.  Pose =(tx,ty,tz,qx,qy,qz,qw) as in lietorch / depth_video.py:69; tau = (rho, theta). */
+/* The ResNet-V2 backbone of the mono-depth prior (weight-standardised convolutions without bias, group norms, bottleneck blocks),
+ * inference only.  Stated in DESIGN.md section 3, "ResNet-V2 backbone".  Everything is stream-ordered, allocates nothing, synchronises
+ * nothing and is bitwise reproducible (no atomics; the order of every sum follows from the shapes alone), and an image gives the same
+ * bits alone and inside any batch.  Activations are channels-last fp16 [image][y][x][channel]; h * w of one image must fit int32,
+ * n <= 65535.
+ * sgr_resnet_conv: ksize 1, 3 or 7, stride 1 or 2, cin a multiple of 8 up to 1024, cout a multiple of 16 in 16..1024.  Output pixel
+ * (oy, ox) of the ho x wo map sums the taps (oy * stride - pad_top + dy, ox * stride - pad_left + dx); taps outside the h x w map read
+ * zero, so the padding after the map is implied.  0 <= pad < ksize, and ho (wo alike) must be (h + pad_top + after - ksize) / stride + 1
+ * for some 0 <= after < ksize.  weight is fp16 [cout][round_up(ksize^2 * cin, 32)], k = tap * cin + c, padding zero.  Without a norm:
+ * v = act(sum + bias), bias fp32 [cout] or NULL, act NONE or RELU, out_kind one of SGR_UPDATE_OUT_*.  With norm = GROUP (groups divides
+ * cout into a power of two of at most 64 channels, at most 256 groups, at least 2 elements per group and image): writes the fp32 sums
+ * to raw [n*ho*wo][cout] and, per tile of 128 pixels and group, (count, s, sum (v - s), sum (v - s)^2) to stats
+ * [n][ceil(ho*wo / 128)][groups][4], s being the group's first sum at the tile's first pixel; bias, act and out are not read.
+ * sgr_resnet_stats: the same statistics of a given fp32 map raw [n*hw][cout].
+ * sgr_resnet_groupnorm: merges the statistics of each (image, group) in fp64 in a fixed order and writes channels-last fp16
+ * relu?(residual + ((v - mean) * rstd * gamma[c] + beta[c])), biased variance, eps = 1e-5, gamma and beta fp32 [cout]; a constant
+ * group gives beta[c] exactly.  residual is channels-last fp16 or NULL.
+ * sgr_resnet_maxpool: 3x3, stride 2, TF "same" padding filled with -inf: [n][h][w][channels] -> [n][ceil(h/2)][ceil(w/2)][channels],
+ * channels a multiple of 8.
+ * sgr_resnet_forward: images [n,3,H,W], H and W multiples of 32 -> the three stage maps l1 [n][H/4*W/4][stage_chs[0]],
+ * l2 [n][H/8*W/8][stage_chs[1]], l3 [n][H/16*W/16][stage_chs[2]] (l3 is the patches layout of sgr_vit_forward).  stem_chs is a
+ * multiple of 16, stage_chs multiples of 64, the bottleneck width stage_chs / 4.  layers[] order: stem, then per block conv1, conv2,
+ * conv3 and, in the first block of a stage, downsample; every convolution has TF "same" padding and is followed by its group norm.
+ * Launches: pack (sgr_encoder_pack, with mean and std when normalize), stem conv, stem norm (ReLU), pool, then per block conv1, norm1
+ * (ReLU), in the first block of a stage downsample conv and norm, conv2 (stride 2 in the first block of stages 1 and 2), norm2 (ReLU),
+ * conv3, norm3 (+ shortcut, ReLU): 4 + sum over stages (6 blocks + 2), of which first_launch <= i <= last_launch are enqueued.
+ * scratch: sgr_resnet_scratch_bytes(n, H, W, stem_chs, stage_chs[0..2]) bytes, 16-byte aligned (0 = unsupported sizes). */
+#define SGR_RESNET_NORM_NONE 0
+#define SGR_RESNET_NORM_GROUP 1
+#define SGR_RESNET_ACT_NONE 0
+#define SGR_RESNET_ACT_RELU 1
+typedef struct SgrResnetConv {
+  const void* src;
+  int32_t src_stride, cin, ksize, stride;
+  int32_t n, h, w;                 /* the input maps */
+  int32_t pad_top, pad_left, ho, wo;
+  const void* weight;
+  int64_t weight_elems;
+  const float* bias;               /* [cout] or NULL; not read with a norm */
+  int32_t cout, norm, act, groups;
+  void* out;
+  int32_t out_kind, out_stride;
+  float* raw;                      /* norm only */
+  int64_t raw_elems;
+  float* stats;                    /* norm only */
+  int64_t stats_elems;
+} SgrResnetConv;
+typedef struct SgrResnetNorm {
+  const float* raw;                /* [n*hw][cout] */
+  const float* stats;              /* [n][ceil(hw / 128)][groups][4] */
+  int32_t n, hw, cout, groups, relu;
+  const float* gamma;
+  const float* beta;
+  const void* residual;            /* [n*hw][residual_stride] fp16 or NULL */
+  int32_t residual_stride;
+  void* out;                       /* [n*hw][out_stride] fp16 */
+  int32_t out_stride;
+} SgrResnetNorm;
+typedef struct SgrResnetLayer {
+  const void* weight;              /* packed, standardised fp16 */
+  int64_t weight_elems;
+  const float* gamma;
+  const float* beta;
+} SgrResnetLayer;
+typedef struct SgrResnetWeights {
+  int32_t stem_chs, stage_chs[3], stage_blocks[3], groups, num_layers;
+  const SgrResnetLayer* layers;    /* host array [num_layers] */
+} SgrResnetWeights;
+typedef struct SgrResnetCall {
+  SgrUpdateTensor images;          /* [n,3,H,W] */
+  int32_t n, H, W, normalize;
+  float mean[3], std_[3];          /* read when normalize != 0 */
+  void* l1;
+  void* l2;
+  void* l3;
+  int32_t first_launch, last_launch;
+} SgrResnetCall;
+size_t sgr_resnet_scratch_bytes(int32_t n, int32_t H, int32_t W, int32_t stem_chs, int32_t chs0, int32_t chs1, int32_t chs2);
+int sgr_resnet_conv(const SgrResnetConv* conv, void* stream);
+int sgr_resnet_stats(const float* raw, int32_t n, int32_t hw, int32_t cout, int32_t groups, float* stats, void* stream);
+int sgr_resnet_groupnorm(const SgrResnetNorm* norm, void* stream);
+int sgr_resnet_maxpool(const void* src, int32_t n, int32_t h, int32_t w, int32_t channels, void* dst, void* stream);
+int sgr_resnet_forward(const SgrResnetWeights* weights, const SgrResnetCall* call, void* scratch, size_t scratch_bytes, void* stream);
+
+/* SE3 ops, batched over n. Pose =(tx,ty,tz,qx,qy,qz,qw) as in lietorch / depth_video.py:69; tau = (rho, theta). */
 int se3_exp(const float* tau, int64_t n, float* pose_out, void* stream);
 int se3_log(const float* pose, int64_t n, float* tau_out, void* stream);
 int se3_inv(const float* pose, int64_t n, float* pose_out, void* stream);

@@ -3,6 +3,9 @@ of the same weights in fp16 (tests/vit_ref.TorchVit and tests/mono_depth_ref.Tor
 i.e. the vendor libraries, and F.scaled_dot_product_attention): the whole transformer at dim 768, depth 12, 1025 tokens, one image, whole
 and launch by launch, and a whole predict of a 480 x 640 image through the default network.  HIP-event medians after a warm-up, the
 two sides alternating in this one process on the same card.  A single launch is timed on the buffers a whole call has left in scratch.
+Then MonoDepth's two backbones, "torch" (the default) and "hip" (splat_slam_amd.resnetv2, csrc/sgr_resnet.hip): the backbone alone and a
+whole predict, the two variants alternating, with the spread of the repeats, the difference of the two predict outputs, and the HIP
+backbone launch by launch with the bytes and operations its shapes imply.
 Writes one JSON file (rewritten after every section, so a run that is cut short leaves what it measured).
 
     timeout 900 python scripts/mono_depth_times.py [--out profiles/mono_depth_times.json] [--reps 10]"""
@@ -21,6 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 DEV = "cuda:0"
 SEED = 7
 PEAK_F16_TFLOPS = 2500.0         # MI355X dense fp16 matrix peak
+PEAK_HBM_TBS = 8.0               # MI355X HBM3E peak bandwidth (spec)
 
 
 def one_time(fn):
@@ -48,6 +52,54 @@ def alternating(hip, ref, reps):
     r["ratio_hip_over_torch"] = round(r["hip"]["ms_median"] / r["torch"]["ms_median"], 4)
     r["hip_not_slower"] = r["hip"]["ms_median"] <= r["torch"]["ms_median"]
     return r
+
+
+def two_variants(torch_fn, hip_fn, reps):
+    """warm both, then torch, hip, torch, hip, ...; the spread of a variant is the distance between the quartiles of its repeats, and
+    the hip variant counts as faster only when the medians differ by more than the larger spread"""
+    torch_fn(), hip_fn(), torch_fn(), hip_fn()
+    tt, th = [], []
+    for _ in range(reps):
+        tt.append(one_time(torch_fn))
+        th.append(one_time(hip_fn))
+    iqr = lambda t: float(np.percentile(t, 75) - np.percentile(t, 25))
+    r = {"torch": summary(tt), "hip": summary(th), "spread_ms": round(max(iqr(tt), iqr(th)), 4)}
+    r["torch"]["ms_max"], r["hip"]["ms_max"] = round(float(np.max(tt)), 4), round(float(np.max(th)), 4)
+    r["ratio_hip_over_torch"] = round(r["hip"]["ms_median"] / r["torch"]["ms_median"], 4)
+    r["hip_faster_beyond_the_spread"] = r["torch"]["ms_median"] - r["hip"]["ms_median"] > r["spread_ms"]
+    return r
+
+
+def backbone_launch_model(cfg, B, H, W):
+    """launch name -> (bytes, GFLOP) of sgr_resnet_forward from the shapes alone: every map read once and written once (taps re-read
+    through the caches are not counted), the packed weights once, the statistics once"""
+    from splat_slam_amd import resnetv2 as RN
+    out, tile = {}, 128
+    groups = cfg.gn_groups
+
+    def conv(name, norm, cin, cout, k, h, w, stride, residual=False):
+        ho, wo = -(-h // stride), -(-w // stride)
+        k_pad = -(-k * k * cin // 32) * 32
+        stats = B * -(-ho * wo // tile) * groups * 16
+        out[name] = (B * h * w * cin * 2 + cout * k_pad * 2 + B * ho * wo * cout * 4 + stats, 2.0 * B * ho * wo * cout * k * k * cin / 1e9)
+        out[norm] = (B * ho * wo * cout * (4 + 2 + (2 if residual else 0)) + stats + cout * 8, 0.0)
+        return ho, wo
+
+    out["pack"] = (B * H * W * (3 * 2 + 8 * 2), 0.0)
+    h, w = conv("stem.conv", "stem.norm", 8, cfg.stem_chs, 7, H, W, 2)
+    out["pool"] = (B * h * w * cfg.stem_chs * 2 + B * (h // 2) * (w // 2) * cfg.stem_chs * 2, 0.0)
+    h, w, cin = h // 2, w // 2, cfg.stem_chs
+    for s, (cout, n) in enumerate(zip(cfg.stage_chs, cfg.stage_layers)):
+        for blk in range(n):
+            p, stride, mid = f"stages.{s}.blocks.{blk}.", 2 if s > 0 and blk == 0 else 1, cout // 4
+            conv(p + "conv1", p + "norm1", cin, mid, 1, h, w, 1)
+            if blk == 0:
+                conv(p + "downsample.conv", p + "downsample.norm", cin, cout, 1, h, w, stride)
+            ho, wo = conv(p + "conv2", p + "norm2", mid, mid, 3, h, w, stride)
+            conv(p + "conv3", p + "norm3", mid, cout, 1, ho, wo, 1, True)
+            h, w, cin = ho, wo, cout
+    assert tuple(out) == RN.LAUNCH_NAMES(cfg)
+    return out
 
 
 def hold_fp16(params):
@@ -127,7 +179,6 @@ def main():
     mcfg = MD.MonoDepthConfig()
     sd = MD.synthetic_state_dict(SEED, mcfg)
     model, torch_model = MD.MonoDepth.from_state_dict(sd, mcfg, DEV), MR.TorchMonoDepth(MR.prepare(sd), mcfg, DEV)
-    del sd
     hold_fp16(torch_model.p), hold_fp16(torch_model.vit.p)
     image = torch.rand(1, 3, 480, 640, generator=torch.Generator().manual_seed(2)).to(DEV)
     p = {"image": [480, 640], "net_size": list(mcfg.net_size)}
@@ -139,6 +190,44 @@ def main():
     res["predict_480x640"] = p
     save()
     print("predict", p["hip"]["ms_median"], "ms; torch", p["torch"]["ms_median"], "ms; ratio", p["ratio_hip_over_torch"], flush=True)
+
+    # ---- the two backbones of MonoDepth: "torch" (the default) and "hip" (csrc/sgr_resnet.hip), alternating in this process ----
+    from splat_slam_amd import resnetv2 as RN
+    hip_model = MD.MonoDepth.from_state_dict(sd, mcfg, DEV, backbone="hip")
+    del sd
+    b = {"net_size": list(mcfg.net_size), "image": [480, 640]}
+    b["backbone"] = two_variants(lambda: model.backbone(xn), lambda: hip_model.backbone(xn), a.reps)
+    b["predict"] = two_variants(lambda: model.predict(image), lambda: hip_model.predict(image), a.reps)
+    b["max_abs_difference_of_the_two_predicts"] = float((model.predict(image) - hip_model.predict(image)).abs().max())
+    res["backbone_torch_vs_hip"] = b
+    p["backbone_hip"] = b["backbone"]["hip"]
+    save()
+    print("backbone torch", b["backbone"]["torch"]["ms_median"], "hip", b["backbone"]["hip"]["ms_median"], "spread", b["backbone"]["spread_ms"],
+          "; predict torch", b["predict"]["torch"]["ms_median"], "hip", b["predict"]["hip"]["ms_median"], "spread", b["predict"]["spread_ms"], flush=True)
+    net = hip_model.backbone
+    call, outs = net._prepare(xn)
+    net._run(call)
+    model_of = backbone_launch_model(mcfg, 1, *mcfg.net_size)
+    launches, by_kind = {}, {}
+    for i, name in enumerate(RN.LAUNCH_NAMES(mcfg)):
+        call.first_launch = call.last_launch = i
+        net._run(call)
+        t = summary([one_time(lambda: net._run(call)) for _ in range(a.reps)])
+        nbytes, gflop = model_of[name]
+        t_bytes, t_flop = nbytes / (PEAK_HBM_TBS * 1e12) * 1e3, gflop / PEAK_F16_TFLOPS
+        t.update({"mbytes": round(nbytes / 1e6, 3), "gflop": round(gflop, 4), "bound": "bytes" if t_bytes >= t_flop else "mfma",
+                  "ms_at_the_bound": round(max(t_bytes, t_flop), 5), "share_of_the_bound": round(max(t_bytes, t_flop) / t["ms_median"], 4)})
+        launches[name] = t
+        kind = name.rsplit(".", 1)[-1] if name.startswith("stages.") else name
+        k = by_kind.setdefault(kind, {"ms": 0.0, "mbytes": 0.0, "gflop": 0.0, "launches": 0})
+        k["ms"], k["mbytes"], k["gflop"], k["launches"] = round(k["ms"] + t["ms_median"], 4), round(k["mbytes"] + t["mbytes"], 3), \
+            round(k["gflop"] + gflop, 4), k["launches"] + 1
+    b["hip_launches"], b["hip_by_kind_of_launch"] = launches, by_kind
+    b["hip_sum_of_launches_ms"] = round(sum(t["ms_median"] for t in launches.values()), 4)
+    b["hip_gflop"], b["hip_mbytes"] = round(sum(v[1] for v in model_of.values()), 2), round(sum(v[0] for v in model_of.values()) / 1e6, 1)
+    b["peak_hbm_tbs"] = PEAK_HBM_TBS
+    save()
+    print("backbone by kind", by_kind, flush=True)
     print(json.dumps({k: v.get("ratio_hip_over_torch") for k, v in res.items() if isinstance(v, dict)}))
 
 

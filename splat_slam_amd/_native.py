@@ -207,6 +207,37 @@ class SgrVitCall(C.Structure):
                 ("first_launch", C.c_int32), ("last_launch", C.c_int32)]
 
 
+class SgrResnetConv(C.Structure):
+    _fields_ = [("src", _fp), ("src_stride", C.c_int32), ("cin", C.c_int32), ("ksize", C.c_int32), ("stride", C.c_int32), ("n", C.c_int32),
+                ("h", C.c_int32), ("w", C.c_int32), ("pad_top", C.c_int32), ("pad_left", C.c_int32), ("ho", C.c_int32), ("wo", C.c_int32),
+                ("weight", _fp), ("weight_elems", C.c_int64), ("bias", _fp), ("cout", C.c_int32), ("norm", C.c_int32), ("act", C.c_int32),
+                ("groups", C.c_int32), ("out", _fp), ("out_kind", C.c_int32), ("out_stride", C.c_int32), ("raw", _fp),
+                ("raw_elems", C.c_int64), ("stats", _fp), ("stats_elems", C.c_int64)]
+
+
+class SgrResnetNorm(C.Structure):
+    _fields_ = [("raw", _fp), ("stats", _fp), ("n", C.c_int32), ("hw", C.c_int32), ("cout", C.c_int32), ("groups", C.c_int32),
+                ("relu", C.c_int32), ("gamma", _fp), ("beta", _fp), ("residual", _fp), ("residual_stride", C.c_int32), ("out", _fp),
+                ("out_stride", C.c_int32)]
+
+
+class SgrResnetLayer(C.Structure):
+    _fields_ = [("weight", _fp), ("weight_elems", C.c_int64), ("gamma", _fp), ("beta", _fp)]
+
+
+class SgrResnetWeights(C.Structure):
+    _fields_ = [("stem_chs", C.c_int32), ("stage_chs", C.c_int32 * 3), ("stage_blocks", C.c_int32 * 3), ("groups", C.c_int32),
+                ("num_layers", C.c_int32), ("layers", C.POINTER(SgrResnetLayer))]
+
+
+class SgrResnetCall(C.Structure):
+    _fields_ = [("images", SgrUpdateTensor), ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("normalize", C.c_int32),
+                ("mean", C.c_float * 3), ("std_", C.c_float * 3), ("l1", _fp), ("l2", _fp), ("l3", _fp), ("first_launch", C.c_int32),
+                ("last_launch", C.c_int32)]
+
+
+SGR_RESNET_NORM_NONE, SGR_RESNET_NORM_GROUP = 0, 1
+SGR_RESNET_ACTS = {"none": 0, "relu": 1}
 SGR_VIT_EPI = {"store_f16": 1, "gelu_f16": 2, "residual": 3, "readout": 4, "embed": 5, "store_f32": 6}
 SGR_ENCODER_NORM_NONE, SGR_ENCODER_NORM_INSTANCE = 0, 1
 SGR_ENCODER_ACTS = {"none": 0, "relu": 1, "split": 2}
@@ -344,6 +375,12 @@ SIGNATURES = {
     "sgr_vit_gemm": (C.c_int, [C.POINTER(SgrVitGemm), _fp]),
     "sgr_vit_attention": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]),
     "sgr_vit_forward": (C.c_int, [C.POINTER(SgrVitWeights), C.POINTER(SgrVitCall), _fp, C.c_size_t, _fp]),
+    "sgr_resnet_scratch_bytes": (C.c_size_t, [C.c_int32] * 7),
+    "sgr_resnet_conv": (C.c_int, [C.POINTER(SgrResnetConv), _fp]),
+    "sgr_resnet_stats": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]),
+    "sgr_resnet_groupnorm": (C.c_int, [C.POINTER(SgrResnetNorm), _fp]),
+    "sgr_resnet_maxpool": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]),
+    "sgr_resnet_forward": (C.c_int, [C.POINTER(SgrResnetWeights), C.POINTER(SgrResnetCall), _fp, C.c_size_t, _fp]),
     "se3_exp": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_log": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_inv": (C.c_int, [_fp, C.c_int64, _fp, _fp]),

@@ -2,8 +2,8 @@
 thirdparty/mono_priors/omnidata/modules/midas/{dpt_depth,blocks,vit}.py), inference only, usable as Slam(..., mono_depth=MonoDepth...).
 
     MonoDepthConfig()                                     the reference's network; every width is a field
-    MonoDepth.from_state_dict(sd, cfg=MonoDepthConfig(), device="cuda")
-    MonoDepth.synthetic(seed, cfg=MonoDepthConfig(), device="cuda")
+    MonoDepth.from_state_dict(sd, cfg=MonoDepthConfig(), device="cuda", backbone="torch")
+    MonoDepth.synthetic(seed, cfg=MonoDepthConfig(), device="cuda", backbone="torch")      backbone: "torch" (the default) or "hip"
     m.forward(x [B,3,H,W]) -> [B,H,W] fp32                H and W multiples of 32; the network on a normalised image
     m.predict(image [1,3,H,W] in [0,1]) -> [H,W] fp32     the reference's predict_mono_depth without its file
     m(timestamp, image)                                   predict(image): the callable Slam, Tracker and MotionFilter take
@@ -15,9 +15,13 @@ thirdparty/mono_priors/omnidata/modules/midas/{dpt_depth,blocks,vit}.py), infere
 Data flow: backbone -> ViT -> reassemble -> layerN_rn -> refinenet4..1 -> head ("Mono-depth prior").  The
 transformer is splat_slam_amd.vit on the sgr_vit_* kernels.  Every stride-1 convolution with symmetric zero padding (the two 1x1
 reassemble maps, the four layerN_rn, the residual units, out_conv, the head) is the MFMA convolution sgr_update_conv with weights packed
-once.  The ResNet-V2 backbone, the one 3x3 stride-2 reassemble convolution, max-pool, adds, ReLU and all resampling are torch ops in
+once.  With backbone="torch" the ResNet-V2 backbone, the one 3x3 stride-2 reassemble convolution and the max-pool are torch ops in
 fp16 with fp32 group norms; those convolutions run the vendor library's deterministic algorithm, so forward and predict repeat bit
-for bit.  A CPU tensor or a missing kernel is an error: there is no eager fallback.
+for bit.  With backbone="hip" self.backbone is a splat_slam_amd.resnetv2.ResNetV2 on the sgr_resnet_* kernels: its stage maps stay
+channels-last (the transformer and layer1_rn / layer2_rn read them without a copy or a pack launch), the stride-2 reassemble
+convolution runs on sgr_resnet_conv, and an image inside a batch gives the bits of the image alone.  Adds, ReLU and all resampling of
+the decoder and the two resizes of predict are torch ops in both settings.  A CPU tensor or a missing kernel is an error: there is no
+eager fallback.
 
 Both state-dict functions accept the checkpoint's {"state_dict": ...} wrapper, whose keys lose their first 6 characters as in the
 reference, and accept and ignore timm's classifier pretrained.model.head.*, the final pretrained.model.norm.* and
@@ -189,17 +193,54 @@ class _Conv:
         B, cin, h, w = x.shape
         dev = x.device
         xs = torch.empty((B * h * w, self.cin_pad), dtype=torch.float16, device=dev)
+        with torch.cuda.device(dev):
+            desc = _tensor_desc(x)
+            nat.check(nat.lib().sgr_update_pack(C.byref(desc), B, cin, h, w, xs.data_ptr(), self.cin_pad, self.cin_pad, _stream(dev)),
+                      "sgr_update_pack")
+        return self.packed(xs, B, h, w, act, out_dtype)
+
+    def packed(self, xs, B, h, w, act="none", out_dtype=torch.float16):
+        """the convolution of a map that is already channels-last fp16 [B * h * w][cin_pad]: no pack launch"""
+        dev = xs.device
+        if xs.dtype != torch.float16 or not xs.is_contiguous() or xs.numel() != B * h * w * self.cin_pad:
+            raise RuntimeError(f"mono_depth: a packed map must be contiguous fp16 [{B * h * w}][{self.cin_pad}], got {tuple(xs.shape)} {xs.dtype}")
         out = torch.empty((B, self.cout, h, w), dtype=out_dtype, device=dev)
         c = nat.SgrUpdateConv()
         c.src0, c.stride0, c.cin, c.ksize, c.E, c.h, c.w = xs.data_ptr(), self.cin_pad, self.cin_pad, self.k, B, h, w
         c.weight, c.weight_elems, c.bias, c.cout, c.act = self.w.data_ptr(), self.w.numel(), self.b.data_ptr(), self.cout, nat.SGR_UPDATE_ACTS[act]
         c.out = out.data_ptr()
         c.out_kind = nat.SGR_UPDATE_OUT_NCHW_F16 if out_dtype == torch.float16 else nat.SGR_UPDATE_OUT_NCHW_F32
+        with torch.cuda.device(dev):
+            nat.check(nat.lib().sgr_update_conv(C.byref(c), _stream(dev)), "sgr_update_conv")
+        return out
+
+
+class _DownConv:
+    """the 3x3 stride-2 reassemble convolution (zero padding 1, with bias) on sgr_resnet_conv, its weights packed once"""
+
+    def __init__(self, w16, b16, device):
+        from splat_slam_amd.resnetv2 import pack_conv
+        self.cout, self.cin = w16.shape[0], w16.shape[1]
+        self.cin_pad = _round_up(self.cin, 8)
+        self.w = pack_conv(w16.to(device))
+        self.b = b16.to(device, torch.float32).contiguous()
+
+    def __call__(self, x):
+        B, cin, h, w = x.shape
+        dev = x.device
+        ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        xs = torch.empty((B * h * w, self.cin_pad), dtype=torch.float16, device=dev)
+        out = torch.empty((B, self.cout, ho, wo), dtype=torch.float16, device=dev)
+        c = nat.SgrResnetConv()
+        c.src, c.src_stride, c.cin, c.ksize, c.stride, c.n, c.h, c.w = xs.data_ptr(), self.cin_pad, self.cin_pad, 3, 2, B, h, w
+        c.pad_top, c.pad_left, c.ho, c.wo = 1, 1, ho, wo
+        c.weight, c.weight_elems, c.bias, c.cout = self.w.data_ptr(), self.w.numel(), self.b.data_ptr(), self.cout
+        c.out, c.out_kind = out.data_ptr(), nat.SGR_UPDATE_OUT_NCHW_F16
         lib = nat.lib()
         with torch.cuda.device(dev):
             desc = _tensor_desc(x)
             nat.check(lib.sgr_update_pack(C.byref(desc), B, cin, h, w, xs.data_ptr(), self.cin_pad, self.cin_pad, _stream(dev)), "sgr_update_pack")
-            nat.check(lib.sgr_update_conv(C.byref(c), _stream(dev)), "sgr_update_conv")
+            nat.check(lib.sgr_resnet_conv(C.byref(c), _stream(dev)), "sgr_resnet_conv")
         return out
 
 
@@ -222,9 +263,15 @@ def _up2(x):
     return F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=True)
 
 
+BACKBONES = ("torch", "hip")
+
+
 class MonoDepth:
-    def __init__(self, sd, cfg=MonoDepthConfig(), device="cuda"):
+    def __init__(self, sd, cfg=MonoDepthConfig(), device="cuda", backbone="torch"):
+        if backbone not in BACKBONES:
+            raise ValueError(f"mono_depth: backbone must be one of {BACKBONES}, got {backbone!r}")
         sd = normalize_state_dict(sd, cfg)
+        self.backbone_kind = backbone
         self.cfg = cfg
         self.device = dev = torch.device(device)
         if dev.type != "cuda":
@@ -248,16 +295,20 @@ class MonoDepth:
                 for j in (1, 2):
                     n = f"scratch.refinenet{i}.resConfUnit{u}.conv{j}"
                     self._c[n] = conv(n)
-        self._down_w = f32("pretrained.act_postprocess4.4.weight").to(torch.float16)       # the 3x3 stride-2 convolution stays torch
-        self._down_b = f32("pretrained.act_postprocess4.4.bias").to(torch.float16)
+        self._down_w = f32("pretrained.act_postprocess4.4.weight").to(torch.float16)       # the 3x3 stride-2 convolution: torch, or
+        self._down_b = f32("pretrained.act_postprocess4.4.bias").to(torch.float16)          # sgr_resnet_conv with backbone="hip"
+        if backbone == "hip":
+            from splat_slam_amd.resnetv2 import ResNetV2
+            self.backbone = ResNetV2({k: v for k, v in sd.items() if k.startswith(_BACKBONE)}, cfg, dev)
+            self._down = _DownConv(self._down_w, self._down_b, dev)
 
     @classmethod
-    def from_state_dict(cls, sd, cfg=MonoDepthConfig(), device="cuda"):
-        return cls(sd, cfg, device)
+    def from_state_dict(cls, sd, cfg=MonoDepthConfig(), device="cuda", backbone="torch"):
+        return cls(sd, cfg, device, backbone)
 
     @classmethod
-    def synthetic(cls, seed, cfg=MonoDepthConfig(), device="cuda"):
-        return cls(synthetic_state_dict(seed, cfg), cfg, device)
+    def synthetic(cls, seed, cfg=MonoDepthConfig(), device="cuda", backbone="torch"):
+        return cls(synthetic_state_dict(seed, cfg), cfg, device, backbone)
 
     # ---- the torch part: ResNet-V2 stem and stages in fp16, group norms in fp32 ----
     def _norm(self, name, x, relu):
@@ -266,7 +317,7 @@ class MonoDepth:
         return (torch.relu(y) if relu else y).to(torch.float16)
 
     def backbone(self, x):
-        """x [B,3,H,W] fp16 -> (stage 0, stage 1, stage 2) at 1/4, 1/8 and 1/16"""
+        """x [B,3,H,W] fp16 -> (stage 0, stage 1, stage 2) at 1/4, 1/8 and 1/16 (backbone="hip" replaces this method by a ResNetV2)"""
         x = self._norm(_BACKBONE + "stem.norm", _conv_same(x, self._std[_BACKBONE + "stem.conv"], 2), True)
         (t, b), (l, r) = same_pad(x.shape[2], 3, 2), same_pad(x.shape[3], 3, 2)
         x = F.max_pool2d(F.pad(x, (l, r, t, b), value=float("-inf")), 3, 2)
@@ -300,14 +351,24 @@ class MonoDepth:
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1 or x.shape[2] < 32 or x.shape[2] % 32 or x.shape[3] < 32 or x.shape[3] % 32:
             raise ValueError(f"mono_depth: x must be [B,3,H,W] with H and W positive multiples of 32, got {tuple(x.shape)}")
         c = self._c
-        l1, l2, l3 = self.backbone(x.to(self.device, torch.float16))
-        tap3, tap4 = self.vit(l3)
+        if self.backbone_kind == "hip":
+            # the stage maps stay channels-last: l3 is the transformer's patches, l1 and l2 are packed inputs of layer1_rn and layer2_rn
+            B, _, H, W = x.shape
+            l1, l2, l3 = self.backbone.channels_last(x.to(self.device, torch.float16))
+            tap3, tap4 = self.vit.tokens(l3, H // 16, W // 16)
+            r4 = self._down(c["pretrained.act_postprocess4.3"](tap4))
+            skip2 = c["scratch.layer2_rn"].packed(l2, B, H // 8, W // 8)
+            skip1 = c["scratch.layer1_rn"].packed(l1, B, H // 4, W // 4)
+        else:
+            l1, l2, l3 = self.backbone(x.to(self.device, torch.float16))
+            tap3, tap4 = self.vit(l3)
+            r4 = _conv2d(c["pretrained.act_postprocess4.3"](tap4), self._down_w, self._down_b, 2, 1)
+            skip2, skip1 = c["scratch.layer2_rn"](l2), c["scratch.layer1_rn"](l1)
         r3 = c["pretrained.act_postprocess3.3"](tap3)
-        r4 = _conv2d(c["pretrained.act_postprocess4.3"](tap4), self._down_w, self._down_b, 2, 1)
         path = self._fusion(4, c["scratch.layer4_rn"](r4))
         path = self._fusion(3, path, c["scratch.layer3_rn"](r3))
-        path = self._fusion(2, path, c["scratch.layer2_rn"](l2))
-        path = self._fusion(1, path, c["scratch.layer1_rn"](l1))
+        path = self._fusion(2, path, skip2)
+        path = self._fusion(1, path, skip1)
         y = c["scratch.output_conv.2"](_up2(c["scratch.output_conv.0"](path)), "relu")
         return c["scratch.output_conv.4"](y, "relu", torch.float32)[:, 0]
 

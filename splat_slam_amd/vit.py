@@ -6,6 +6,7 @@ gfx950 kernels `sgr_vit_*` (include/splat_hip.h, csrc/sgr_vit.hip).  Inference o
     VisionTransformer.from_state_dict(sd, cfg=VitConfig(), device="cuda")
     VisionTransformer.synthetic(seed, cfg=VitConfig(), device="cuda")      weights of synthetic_state_dict(seed, cfg)
     vit(patch_features [B,cin,gh,gw]) -> (tap_a, tap_b)                     each fp16 [B,dim,gh,gw]
+    vit.tokens(patches [B,gh*gw,cin] fp16, gh, gw) -> (tap_a, tap_b)        the same on channels-last features, without the copy
     synthetic_state_dict(seed, cfg)      fp32 CPU tensors by the closed-form integer hash of update_op (name, flat index, seed)
     normalize_state_dict(sd, cfg)        validation alone (touches no device); state_shapes(cfg) lists the keys
     resize_pos_embed(pos, g0, gh, gw)    the reference's _resize_pos_embed: bilinear, align_corners=False, the class row kept
@@ -280,7 +281,9 @@ class VisionTransformer:
         if x.dim() != 4 or x.shape[1] != self.cfg.cin or min(x.shape) < 1 or x.dtype not in (torch.float16, torch.float32):
             raise RuntimeError(f"vit: patch_features must be a non-empty fp16 or fp32 [B,{self.cfg.cin},gh,gw], got {tuple(x.shape)} {x.dtype}")
         B, _, gh, gw = x.shape
-        patches = x.permute(0, 2, 3, 1).to(torch.float16).contiguous()
+        return self._record(x.permute(0, 2, 3, 1).to(torch.float16).contiguous(), B, gh, gw)
+
+    def _record(self, patches, B, gh, gw):
         pos = self.pos_table(gh, gw)
         outs = tuple(torch.empty((B, self.cfg.dim, gh, gw), dtype=torch.float16, device=self.device) for _ in range(2))
         call = nat.SgrVitCall()
@@ -299,5 +302,17 @@ class VisionTransformer:
 
     def __call__(self, patch_features):
         call, outs, _ = self._prepare(patch_features)
+        self._run(call)
+        return outs
+
+    def tokens(self, patches, gh, gw):
+        """the transformer on patch features that are already channels-last: patches fp16 [B, gh * gw, cin], contiguous, as a backbone
+        on this library's kernels leaves them -> (tap_a, tap_b); no copy is made"""
+        _gpu("patches", patches, torch.float16)
+        if patches.device != self.device:
+            raise RuntimeError(f"vit: patches is on {patches.device}, the transformer on {self.device}")
+        if patches.dim() != 3 or gh < 1 or gw < 1 or patches.shape[0] < 1 or tuple(patches.shape[1:]) != (gh * gw, self.cfg.cin):
+            raise RuntimeError(f"vit: patches must be [B,{gh * gw},{self.cfg.cin}], got {tuple(patches.shape)}")
+        call, outs, _ = self._record(patches, patches.shape[0], gh, gw)
         self._run(call)
         return outs
