@@ -1,0 +1,196 @@
+// The convolution tile shared by the update operator (sgr_update.hip), the encoders (sgr_encoder.hip) and the ResNet-V2 backbone
+// (sgr_resnet.hip), the pieces of the two norms that are the same in both, and the host helpers of these files and of sgr_vit.hip.
+// DESIGN.md section 3, "Update operator", describes the tile.
+//
+// The GEMM is D[n][m] = sum_k W[n][k] X[m][k] with m a pixel, n an output channel and k = tap * cin + channel: the weights are the A
+// operand of mfma_f32_16x16x32_f16 and the pixels the B operand, so that a lane of the accumulator holds four consecutive output channels
+// of one pixel.  One workgroup of kThreads: kBM pixels x BN output channels.  Wave v owns pixels [32v, 32v + 32) as two 16-wide B tiles
+// and all BN / 16 A tiles, and acc[t][j][r] is output channel n0 + 16 t + 4 (lane >> 4) + r of pixel m0 + 32 v + 16 j + (lane & 15).
+// Every sum has a fixed order (the MFMA k order, serial loops elsewhere): no atomics, bitwise reproducible.
+#pragma once
+
+#include <type_traits>
+
+#include "sgr_common.h"
+
+namespace sgr {
+
+typedef _Float16 half_t;
+typedef __attribute__((ext_vector_type(4))) _Float16 half4;
+typedef __attribute__((ext_vector_type(8))) _Float16 half8;
+typedef __attribute__((ext_vector_type(4))) float floatx4;
+
+constexpr int kThreads = 256;
+constexpr int kBM = 128;                    // pixels of one workgroup: 4 waves x 2 tiles of 16
+constexpr int kBK = 32;                     // one MFMA k step
+constexpr int kRow = kBK + 8;               // halfs per LDS row: 80 bytes, so that the 16 rows of a fragment read spread over the banks
+constexpr float kEps = 1e-5f;               // of the instance and the group norm
+
+// The k loop of one workgroup: Xs [kBM][kRow], Ws [BN][kRow] in LDS, weight the packed [.][k_pad] rows, acc zeroed here.  Staging: thread
+// t loads the 16-byte chunk k = 8 (t & 3) of pixel rows t >> 2 and 64 + (t >> 2) and of weight row n0 + (t >> 2) into registers one k step
+// ahead of the MFMAs that consume the previous step out of LDS.  gather(i, tv, ty, tx, ch) returns the chunk of pixel row t >> 2 + 64 i at
+// tap (ty, tx) of the KS x KS window, channels ch .. ch + 7, or zeros for a halo, a pixel past the end or, with tv false, the zero tail
+// of a k_pad that is no multiple of the taps: which image, which stride and which padding is the caller's business alone.
+template <int KS, int BN, class Gather>
+__device__ __forceinline__ void conv_mma_mainloop(half_t* Xs, half_t* Ws, const half_t* weight, int n0, int k_pad, int cin, Gather&& gather,
+                                                  floatx4 (&acc)[BN / 16][2]) {
+  constexpr int NT = BN / 16;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int kc = tid & 3, srow = tid >> 2;
+  const bool wv = tid < BN * 4;
+  const half_t* wp = weight + (size_t)(n0 + (wv ? srow : 0)) * k_pad + kc * 8;
+
+  int tap = (kc * 8) / cin, ch = (kc * 8) % cin;             // this thread's chunk of the current k step
+  half8 xr[2], wr;
+  auto gload = [&](int kt) {
+    const int ty = tap / KS, tx = tap % KS;
+    const bool tv = tap < KS * KS;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) xr[i] = gather(i, tv, ty, tx, ch);
+    if (wv) wr = *(const half8*)(wp + (size_t)kt * kBK);
+  };
+
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[t][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+
+  const int nk = k_pad / kBK;
+  gload(0);
+  for (int kt = 0; kt < nk; ++kt) {
+    *(half8*)&Xs[srow * kRow + kc * 8] = xr[0];
+    *(half8*)&Xs[(srow + 64) * kRow + kc * 8] = xr[1];
+    if (wv) *(half8*)&Ws[srow * kRow + kc * 8] = wr;
+    __syncthreads();
+    if (kt + 1 < nk) {
+      ch += kBK;
+      while (ch >= cin) {
+        ch -= cin;
+        ++tap;
+      }
+      gload(kt + 1);
+    }
+    half8 bf[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) bf[j] = *(const half8*)&Xs[(wave * 32 + j * 16 + (lane & 15)) * kRow + (lane >> 4) * 8];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const half8 af = *(const half8*)&Ws[(t * 16 + (lane & 15)) * kRow + (lane >> 4) * 8];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[j], acc[t][j], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+}
+
+// The shifted sums of a tile for a norm: with d = acc - shift_of(n) over the valid pixels, red[0][wave][n] = S1 = sum d and
+// red[1][wave][n] = S2 = sum d^2 of channel n of the tile (n in 0 .. BN - 1) over the wave's 32 pixels, the 16 pixel lanes summed by a
+// butterfly.  The caller chooses the shift, puts a barrier behind this and folds the four waves of red.
+template <int BN, class Shift>
+__device__ __forceinline__ void tile_shifted_sums(const floatx4 (&acc)[BN / 16][2], const bool (&valid)[2], Shift&& shift_of,
+                                                  float (&red)[2][4][BN]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int t = 0; t < BN / 16; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int n = t * 16 + (lane >> 4) * 4 + r;
+      const float sh = shift_of(n);
+      const float d0 = valid[0] ? acc[t][0][r] - sh : 0.f, d1 = valid[1] ? acc[t][1][r] - sh : 0.f;
+      float s1 = d0 + d1, s2 = d0 * d0 + d1 * d1;
+#pragma unroll
+      for (int d = 1; d < 16; d <<= 1) {
+        s1 += __shfl_xor(s1, d);
+        s2 += __shfl_xor(s2, d);
+      }
+      if ((lane & 15) == 0) {
+        red[0][wave][n] = s1;
+        red[1][wave][n] = s2;
+      }
+    }
+}
+
+// The merge of the per-tile statistics {count, shift, S1, S2} of one image, st [tiles][G], by a whole workgroup in fp64 about s0, the
+// shift of tile 0: with d = s_i - s0, A = sum (n_i d + S1_i) and B = sum (S2_i + 2 d S1_i + n_i d^2) are the sums of (v - s0) and
+// (v - s0)^2 over the N elements of a statistic, so mean = s0 + A / N and M2 = B - A^2 / N.  Thread (slot, g) takes the tiles slot,
+// slot + S, ... (S = kThreads / G) in ascending order, the slots are then added in ascending order: the result depends on the map
+// alone.  mu[g] = mean and rs[g] = 1 / sqrt(M2 / N + eps) are rounded once to fp32; a barrier follows.  pa, pb: kThreads doubles of LDS.
+__device__ __forceinline__ void merge_tile_stats(const floatx4* st, int tiles, int G, double N, double* pa, double* pb, float* mu, float* rs) {
+  const int tid = threadIdx.x, g = tid % G, slot = tid / G, S = kThreads / G;
+  const double s0 = (double)st[g][1];
+  double A = 0.0, B = 0.0;
+  if (slot < S)
+    for (int t = slot; t < tiles; t += S) {
+      const floatx4 q = st[(int64_t)t * G + g];
+      const double n = q[0], d = (double)q[1] - s0, s1 = q[2], s2 = q[3];
+      A += n * d + s1;
+      B += s2 + 2.0 * d * s1 + n * d * d;
+    }
+  pa[tid] = A;
+  pb[tid] = B;
+  __syncthreads();
+  if (tid < G) {
+    for (int s = 1; s < S; ++s) {
+      A += pa[s * G + tid];
+      B += pb[s * G + tid];
+    }
+    const double mean = s0 + A / N, var = fmax((B - A * A / N) / N, 0.0);
+    mu[tid] = (float)mean;
+    rs[tid] = (float)(1.0 / sqrt(var + (double)kEps));
+  }
+  __syncthreads();
+}
+
+// v = output channels nb .. nb + 3 of pixel p of image img (gm = img * HW + p) under the four SGR_UPDATE_OUT_* kinds
+__device__ __forceinline__ void store_out4(void* out, int out_kind, int out_stride, const floatx4& v, int64_t gm, int img, int p, int nb, int cout,
+                                           int HW) {
+  switch (out_kind) {
+    case SGR_UPDATE_OUT_CL_F16: {
+      half4 o;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[r] = (half_t)v[r];
+      *(half4*)&((half_t*)out)[gm * out_stride + nb] = o;
+      break;
+    }
+    case SGR_UPDATE_OUT_CL_F32: *(floatx4*)&((float*)out)[gm * out_stride + nb] = v; break;
+    case SGR_UPDATE_OUT_NCHW_F16:
+#pragma unroll
+      for (int r = 0; r < 4; ++r) ((half_t*)out)[((int64_t)img * cout + nb + r) * HW + p] = (half_t)v[r];
+      break;
+    default:
+#pragma unroll
+      for (int r = 0; r < 4; ++r) ((float*)out)[((int64_t)img * cout + nb + r) * HW + p] = v[r];
+      break;
+  }
+}
+
+// ---- host helpers
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+inline int tiles_of(int64_t hw) { return (int)((hw + kBM - 1) / kBM); }
+inline bool map_ok(int n, int h, int w) { return n >= 1 && n <= 65535 && h >= 1 && w >= 1 && (int64_t)h * w <= 0x7fffffff - kBM; }
+
+// Carves a scratch buffer into 256-byte aligned pieces; with a null base only the size is counted.
+struct Carver {
+  void* base;
+  size_t off = 0;
+  void* take(size_t nbytes) {
+    void* p = base ? (char*)base + off : nullptr;
+    off += align_up(nbytes);
+    return p;
+  }
+};
+
+// launch(integral_constant<KS>, integral_constant<BN>) for the kernel size (1, 3, else 7) and the one of BNs that equals bn
+template <int... BNs, class Launch>
+inline void dispatch_conv(int ksize, int bn, Launch&& launch) {
+  auto by_bn = [&](auto ks) { (void)((bn == BNs && (launch(ks, std::integral_constant<int, BNs>{}), true)) || ...); };
+  if (ksize == 1)
+    by_bn(std::integral_constant<int, 1>{});
+  else if (ksize == 3)
+    by_bn(std::integral_constant<int, 3>{});
+  else
+    by_bn(std::integral_constant<int, 7>{});
+}
+
+}  // namespace sgr

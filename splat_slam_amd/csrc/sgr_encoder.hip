@@ -5,40 +5,28 @@
 //                         fused epilogue, or, with an instance norm, the raw fp32 sums with per-tile statistics followed by one apply launch
 //   sgr_encoder_forward   a whole encoder: 32 (fnet) or 17 (cnet) stream-ordered launches, no host synchronisation
 // Layouts, the launch list, the rounding points and the statistics scheme are described in DESIGN.md section 3, "Encoders".  The GEMM is
-// that of sgr_update.hip (weights the A operand, pixels the B operand, k = tap * cin + channel) with three differences: a workgroup's 128
-// pixels belong to one image (blockIdx.z), the gather takes a stride, and output channels come in tiles of 32 or 64.  Every sum has a fixed
-// order: no atomics, bitwise reproducible, and image i of a batch gives the bits of that image alone.
+// the shared tile of sgr_conv_mma.h; here a workgroup's 128 output pixels belong to one image (blockIdx.z), the gather takes a stride, and
+// output channels come in tiles of 32 or 64.  Every sum has a fixed order: no atomics, bitwise reproducible, and image i of a batch gives
+// the bits of that image alone.
 #include <cstdint>
 
-#include "sgr_common.h"
+#include "sgr_conv_mma.h"
 
 namespace sgr {
 int set_error(int code, const char* fmt, ...);
 
 namespace {
 
-typedef _Float16 half_t;
-typedef __attribute__((ext_vector_type(4))) _Float16 half4;
-typedef __attribute__((ext_vector_type(8))) _Float16 half8;
-typedef __attribute__((ext_vector_type(4))) float floatx4;
-
-constexpr int kThreads = 256;
-constexpr int kBM = 128;                    // output pixels of one workgroup: 4 waves x 2 tiles of 16
-constexpr int kBK = 32;                     // one MFMA k step
-constexpr int kRow = kBK + 8;               // halfs per LDS row: 80 bytes, so that the 16 rows of a fragment read spread over the banks
 constexpr int kInPad = 8;                   // the 3 image channels padded to one 16-byte chunk
 constexpr int kApplyPixels = 512;           // pixels of one workgroup of the apply launch
 constexpr int kLayers = SGR_ENCODER_LAYERS;
-constexpr float kEps = 1e-5f;
 
 struct ConvArgs {
   SgrEncoderConv c;
   int ho, wo, HWo, k_pad, tiles;
 };
 
-// One workgroup: kBM output pixels of image blockIdx.z x BN output channels.  Wave v owns pixels [32v, 32v + 32) as two 16-wide B tiles
-// and all BN / 16 A tiles.  Staging: thread t loads the 16-byte chunk k = 8 (t & 3) of pixel rows t >> 2 and 64 + (t >> 2) and of weight
-// row t >> 2 into registers one k step ahead of the MFMAs that consume the previous step out of LDS.
+// The shared tile on the kBM output pixels m0 .. of image blockIdx.z: zero padding KS / 2, stride c.stride.
 template <int KS, int BN>
 __global__ void __launch_bounds__(kThreads) enc_conv_kernel(const ConvArgs a) {
   constexpr int NT = BN / 16;
@@ -49,70 +37,27 @@ __global__ void __launch_bounds__(kThreads) enc_conv_kernel(const ConvArgs a) {
   const SgrEncoderConv& c = a.c;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int img = blockIdx.z, m0 = blockIdx.x * kBM, n0 = blockIdx.y * BN;
-  const int kc = tid & 3, srow = tid >> 2;
   const half_t* src = (const half_t*)c.src + (int64_t)img * c.h * c.w * c.src_stride;
 
   int iy[2], ix[2];
   bool pv[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    const int m = m0 + srow + 64 * i;
+    const int m = m0 + (tid >> 2) + 64 * i;
     pv[i] = m < a.HWo;
     const int mm = pv[i] ? m : 0, oy = mm / a.wo;
     iy[i] = oy * c.stride;
     ix[i] = (mm - oy * a.wo) * c.stride;
   }
-  const bool wv = tid < BN * 4;
-  const half_t* wp = (const half_t*)c.weight + (size_t)(n0 + (wv ? srow : 0)) * a.k_pad + kc * 8;
-
-  int tap = (kc * 8) / c.cin, ch = (kc * 8) % c.cin;       // this thread's chunk of the current k step
-  half8 xr[2], wr;
-  auto gload = [&](int kt) {
-    const int dy = tap / KS - KS / 2, dx = tap % KS - KS / 2;
-    const bool tv = tap < KS * KS;                           // the zero tail of a k_pad that is no multiple of the taps
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int yy = iy[i] + dy, xx = ix[i] + dx;
-      half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (pv[i] && tv && (unsigned)yy < (unsigned)c.h && (unsigned)xx < (unsigned)c.w)
-        v = *(const half8*)(src + ((int64_t)yy * c.w + xx) * c.src_stride + ch);
-      xr[i] = v;
-    }
-    if (wv) wr = *(const half8*)(wp + (size_t)kt * kBK);
+  auto gather = [&](int i, bool tv, int ty, int tx, int ch) {
+    const int yy = iy[i] + ty - KS / 2, xx = ix[i] + tx - KS / 2;
+    half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (pv[i] && tv && (unsigned)yy < (unsigned)c.h && (unsigned)xx < (unsigned)c.w)
+      v = *(const half8*)(src + ((int64_t)yy * c.w + xx) * c.src_stride + ch);
+    return v;
   };
-
   floatx4 acc[NT][2];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[t][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-
-  const int nk = a.k_pad / kBK;
-  gload(0);
-  for (int kt = 0; kt < nk; ++kt) {
-    *(half8*)&Xs[srow * kRow + kc * 8] = xr[0];
-    *(half8*)&Xs[(srow + 64) * kRow + kc * 8] = xr[1];
-    if (wv) *(half8*)&Ws[srow * kRow + kc * 8] = wr;
-    __syncthreads();
-    if (kt + 1 < nk) {
-      ch += kBK;
-      while (ch >= c.cin) {
-        ch -= c.cin;
-        ++tap;
-      }
-      gload(kt + 1);
-    }
-    half8 bf[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) bf[j] = *(const half8*)&Xs[(wave * 32 + j * 16 + (lane & 15)) * kRow + (lane >> 4) * 8];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const half8 af = *(const half8*)&Ws[(t * 16 + (lane & 15)) * kRow + (lane >> 4) * 8];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[j], acc[t][j], 0, 0, 0);
-    }
-    __syncthreads();
-  }
+  conv_mma_mainloop<KS, BN>(Xs, Ws, (const half_t*)c.weight, n0, a.k_pad, c.cin, gather, acc);
 
   // acc[t][j][r] is output channel n0 + 16 t + 4 (lane >> 4) + r of pixel m0 + 32 wave + 16 j + (lane & 15) of this image
   bool valid[2];
@@ -147,24 +92,7 @@ __global__ void __launch_bounds__(kThreads) enc_conv_kernel(const ConvArgs a) {
     __syncthreads();
     if (tid < BN) shift[tid] = (((red[0][0][tid] + red[0][1][tid]) + red[0][2][tid]) + red[0][3][tid]) / cnt;
     __syncthreads();
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = t * 16 + (lane >> 4) * 4 + r;
-        const float sh = shift[n];
-        const float d0 = valid[0] ? acc[t][0][r] - sh : 0.f, d1 = valid[1] ? acc[t][1][r] - sh : 0.f;
-        float s1 = d0 + d1, s2 = d0 * d0 + d1 * d1;
-#pragma unroll
-        for (int d = 1; d < 16; d <<= 1) {
-          s1 += __shfl_xor(s1, d);
-          s2 += __shfl_xor(s2, d);
-        }
-        if ((lane & 15) == 0) {
-          red[0][wave][n] = s1;
-          red[1][wave][n] = s2;
-        }
-      }
+    tile_shifted_sums<BN>(acc, valid, [&](int n) { return shift[n]; }, red);
     __syncthreads();
     if (tid < BN) {
       const float s1 = ((red[0][0][tid] + red[0][1][tid]) + red[0][2][tid]) + red[0][3][tid];
@@ -198,24 +126,7 @@ __global__ void __launch_bounds__(kThreads) enc_conv_kernel(const ConvArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = fmaxf((float)x[r] + v[r], 0.f);
       }
-      switch (c.out_kind) {
-        case SGR_UPDATE_OUT_CL_F16: {
-          half4 o;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = (half_t)v[r];
-          *(half4*)&((half_t*)c.out)[gm[j] * c.out_stride + nb] = o;
-          break;
-        }
-        case SGR_UPDATE_OUT_CL_F32: *(floatx4*)&((float*)c.out)[gm[j] * c.out_stride + nb] = v; break;
-        case SGR_UPDATE_OUT_NCHW_F16:
-#pragma unroll
-          for (int r = 0; r < 4; ++r) ((half_t*)c.out)[((int64_t)img * c.cout + nb + r) * a.HWo + p] = (half_t)v[r];
-          break;
-        default:
-#pragma unroll
-          for (int r = 0; r < 4; ++r) ((float*)c.out)[((int64_t)img * c.cout + nb + r) * a.HWo + p] = v[r];
-          break;
-      }
+      store_out4(c.out, c.out_kind, c.out_stride, v, gm[j], img, p, nb, c.cout, a.HWo);
     }
   }
 }
@@ -229,40 +140,13 @@ struct ApplyArgs {
 };
 
 // The second launch of a normalised convolution, grid (pixel blocks, images).  Every workgroup first merges the per-tile statistics of
-// its image in fp64 about s0, the shift of tile 0: with d = s_i - s0, A = sum (n_i d + S1_i) and B = sum (S2_i + 2 d S1_i + n_i d^2) are
-// the sums of (v - s0) and (v - s0)^2 over the map, so mean = s0 + A / N and M2 = B - A^2 / N.  Thread (slot, channel) takes the tiles
-// slot, slot + S, ... (S = 256 / C) in ascending order, the slots are then added in ascending order: the result depends on the map alone.
-// mean and 1 / sqrt(M2 / N + eps) are rounded once to fp32; then y = (v - mean) * rstd, ReLU, + residual, ReLU in fp32, one rounding to
-// the output.  One thread per (pixel, 8 channels).
+// its image, one statistic per channel (merge_tile_stats, sgr_conv_mma.h); then y = (v - mean) * rstd, ReLU, + residual, ReLU in fp32,
+// one rounding to the output.  One thread per (pixel, 8 channels).
 __global__ void __launch_bounds__(kThreads) enc_apply_kernel(const ApplyArgs a) {
   __shared__ double pa[kThreads], pb[kThreads];
   __shared__ float mu[128], rs[128];
   const int tid = threadIdx.x, img = blockIdx.y, C = a.C;
-  {
-    const int ch = tid % C, slot = tid / C, S = kThreads / C;
-    const floatx4* st = (const floatx4*)a.stats + (int64_t)img * a.tiles * C;
-    const double s0 = (double)st[ch][1];
-    double A = 0.0, B = 0.0;
-    for (int t = slot; t < a.tiles; t += S) {
-      const floatx4 q = st[(int64_t)t * C + ch];
-      const double n = q[0], d = (double)q[1] - s0, s1 = q[2], s2 = q[3];
-      A += n * d + s1;
-      B += s2 + 2.0 * d * s1 + n * d * d;
-    }
-    pa[tid] = A;
-    pb[tid] = B;
-    __syncthreads();
-    if (tid < C) {
-      for (int s = 1; s < S; ++s) {
-        A += pa[s * C + tid];
-        B += pb[s * C + tid];
-      }
-      const double N = (double)a.HWo, mean = s0 + A / N, var = fmax((B - A * A / N) / N, 0.0);
-      mu[tid] = (float)mean;
-      rs[tid] = (float)(1.0 / sqrt(var + (double)kEps));
-    }
-    __syncthreads();
-  }
+  merge_tile_stats((const floatx4*)a.stats + (int64_t)img * a.tiles * C, a.tiles, C, (double)a.HWo, pa, pb, mu, rs);
   const int chunks = C / 8, p0 = blockIdx.x * kApplyPixels;
   for (int i = tid; i < kApplyPixels * chunks; i += kThreads) {
     const int p = p0 + i / chunks, j = i % chunks;
@@ -317,13 +201,7 @@ __global__ void __launch_bounds__(kThreads) enc_pack_kernel(const PackArgs a, ha
   *(half8*)&dst[((int64_t)img * a.HW + p) * kInPad] = v;
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline int out_size(int v, int stride) { return (v - 1) / stride + 1; }
-inline int tiles_of(int64_t hw) { return (int)((hw + kBM - 1) / kBM); }
-
-bool map_ok(int n, int h, int w) { return n >= 1 && n <= 65535 && h >= 1 && w >= 1 && (int64_t)h * w <= 0x7fffffff - kBM; }
 
 int launch_conv(const SgrEncoderConv& c, hipStream_t stream) {
   if (!c.src || !c.weight || !c.bias) return set_error(SGR_ERR_INVALID, "encoder_conv: null argument");
@@ -372,19 +250,9 @@ int launch_conv(const SgrEncoderConv& c, hipStream_t stream) {
   }
   const int bn = c.cout == 32 ? 32 : 64;
   const dim3 grid((unsigned)a.tiles, (unsigned)(c.cout / bn), (unsigned)c.n), block(kThreads);
-#define SGR_ENCODER_LAUNCH(KS)                                                                  \
-  if (bn == 32)                                                                                 \
-    hipLaunchKernelGGL((enc_conv_kernel<KS, 32>), grid, block, 0, stream, a);                   \
-  else                                                                                          \
-    hipLaunchKernelGGL((enc_conv_kernel<KS, 64>), grid, block, 0, stream, a)
-  if (c.ksize == 1) {
-    SGR_ENCODER_LAUNCH(1);
-  } else if (c.ksize == 3) {
-    SGR_ENCODER_LAUNCH(3);
-  } else {
-    SGR_ENCODER_LAUNCH(7);
-  }
-#undef SGR_ENCODER_LAUNCH
+  dispatch_conv<32, 64>(c.ksize, bn, [&](auto ks, auto bnc) {
+    hipLaunchKernelGGL((enc_conv_kernel<decltype(ks)::value, decltype(bnc)::value>), grid, block, 0, stream, a);
+  });
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "encoder_conv launch failed");
 }
 
@@ -423,12 +291,7 @@ Plan carve(void* base, int n, int H, int W, bool norm) {
   Plan s;
   s.h[0] = H, s.w[0] = W;
   for (int l = 1; l < 4; ++l) s.h[l] = out_size(s.h[l - 1], 2), s.w[l] = out_size(s.w[l - 1], 2);
-  size_t off = 0;
-  auto take = [&](size_t nbytes) {
-    void* p = base ? (char*)base + off : nullptr;
-    off += align256(nbytes);
-    return p;
-  };
+  Carver cv{base};
   int64_t act_elems = 0;
   s.raw_elems = s.stats_elems = 0;
   for (int l = 1; l < 4; ++l) {
@@ -438,11 +301,11 @@ Plan carve(void* base, int n, int H, int W, bool norm) {
     s.stats_elems = s.stats_elems > st ? s.stats_elems : st;
   }
   s.raw_elems = act_elems;
-  s.xin = (half_t*)take((size_t)n * H * W * kInPad * 2);
-  for (int i = 0; i < 4; ++i) s.act[i] = (half_t*)take((size_t)act_elems * 2);
-  s.raw = (float*)take(norm ? (size_t)s.raw_elems * 4 : 0);
-  s.stats = (float*)take(norm ? (size_t)s.stats_elems * 4 : 0);
-  s.bytes = off;
+  s.xin = (half_t*)cv.take((size_t)n * H * W * kInPad * 2);
+  for (int i = 0; i < 4; ++i) s.act[i] = (half_t*)cv.take((size_t)act_elems * 2);
+  s.raw = (float*)cv.take(norm ? (size_t)s.raw_elems * 4 : 0);
+  s.stats = (float*)cv.take(norm ? (size_t)s.stats_elems * 4 : 0);
+  s.bytes = cv.off;
   return s;
 }
 

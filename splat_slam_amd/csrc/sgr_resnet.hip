@@ -7,41 +7,30 @@
 //   sgr_resnet_groupnorm   the second launch of a norm: merges the statistics in fp64, writes relu?(residual + affine(normalised))
 //   sgr_resnet_maxpool     3x3 stride 2, TF "same" padding filled with -inf
 //   sgr_resnet_forward     a whole backbone: 4 + sum over stages (6 blocks + 2) stream-ordered launches, no host synchronisation
-// Layouts, the launch list and the statistics scheme are described in DESIGN.md section 3, "ResNet-V2 backbone".  The GEMM is that of
-// sgr_encoder.hip (weights the A operand, pixels the B operand, k = tap * cin + channel, a workgroup's 128 pixels belong to one image)
-// with explicit padding and output-channel tiles of 16, 32 or 64.  Every sum has a fixed order: no atomics, bitwise reproducible, and
-// image i of a batch gives the bits of that image alone.
+// Layouts, the launch list and the statistics scheme are described in DESIGN.md section 3, "ResNet-V2 backbone".  The GEMM is the shared
+// tile of sgr_conv_mma.h; here a workgroup's 128 output pixels belong to one image (blockIdx.z), the padding is explicit and output
+// channels come in tiles of 16, 32 or 64.  Every sum has a fixed order: no atomics, bitwise reproducible, and image i of a batch gives
+// the bits of that image alone.
 #include <cstdint>
 
-#include "sgr_common.h"
+#include "sgr_conv_mma.h"
 
 namespace sgr {
 int set_error(int code, const char* fmt, ...);
 
 namespace {
 
-typedef _Float16 half_t;
-typedef __attribute__((ext_vector_type(4))) _Float16 half4;
-typedef __attribute__((ext_vector_type(8))) _Float16 half8;
-typedef __attribute__((ext_vector_type(4))) float floatx4;
-
-constexpr int kThreads = 256;
-constexpr int kBM = 128;                    // output pixels of one workgroup: 4 waves x 2 tiles of 16
-constexpr int kBK = 32;                     // one MFMA k step
-constexpr int kRow = kBK + 8;               // halfs per LDS row: 80 bytes, so that the 16 rows of a fragment read spread over the banks
 constexpr int kInPad = 8;                   // the 3 image channels padded to one 16-byte chunk
 constexpr int kMaxGroups = 256;             // one merge thread per group
 constexpr int kMaxChannels = 1024;
-constexpr float kEps = 1e-5f;
 
 struct ConvArgs {
   SgrResnetConv c;
   int HWo, k_pad, tiles, cshift;            // cshift = log2(channels per group)
 };
 
-// One workgroup: kBM output pixels of image blockIdx.z x BN output channels.  Wave v owns pixels [32v, 32v + 32) as two 16-wide B tiles
-// and all BN / 16 A tiles.  Staging: thread t loads the 16-byte chunk k = 8 (t & 3) of pixel rows t >> 2 and 64 + (t >> 2) and of weight
-// row t >> 2 into registers one k step ahead of the MFMAs that consume the previous step out of LDS.
+// The shared tile on the kBM output pixels m0 .. of image blockIdx.z: stride c.stride, c.pad_top rows and c.pad_left columns of zeros
+// in front, whatever the output size needs behind.
 template <int KS, int BN>
 __global__ void __launch_bounds__(kThreads) resnet_conv_kernel(const ConvArgs a) {
   constexpr int NT = BN / 16;
@@ -52,70 +41,27 @@ __global__ void __launch_bounds__(kThreads) resnet_conv_kernel(const ConvArgs a)
   const SgrResnetConv& c = a.c;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int img = blockIdx.z, m0 = blockIdx.x * kBM, n0 = blockIdx.y * BN;
-  const int kc = tid & 3, srow = tid >> 2;
   const half_t* src = (const half_t*)c.src + (int64_t)img * c.h * c.w * c.src_stride;
 
   int iy[2], ix[2];
   bool pv[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    const int m = m0 + srow + 64 * i;
+    const int m = m0 + (tid >> 2) + 64 * i;
     pv[i] = m < a.HWo;
     const int mm = pv[i] ? m : 0, oy = mm / c.wo;
     iy[i] = oy * c.stride - c.pad_top;
     ix[i] = (mm - oy * c.wo) * c.stride - c.pad_left;
   }
-  const bool wv = tid < BN * 4;
-  const half_t* wp = (const half_t*)c.weight + (size_t)(n0 + (wv ? srow : 0)) * a.k_pad + kc * 8;
-
-  int tap = (kc * 8) / c.cin, ch = (kc * 8) % c.cin;       // this thread's chunk of the current k step
-  half8 xr[2], wr;
-  auto gload = [&](int kt) {
-    const int dy = tap / KS, dx = tap % KS;
-    const bool tv = tap < KS * KS;                           // the zero tail of a k_pad that is no multiple of the taps
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int yy = iy[i] + dy, xx = ix[i] + dx;
-      half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (pv[i] && tv && (unsigned)yy < (unsigned)c.h && (unsigned)xx < (unsigned)c.w)
-        v = *(const half8*)(src + ((int64_t)yy * c.w + xx) * c.src_stride + ch);
-      xr[i] = v;
-    }
-    if (wv) wr = *(const half8*)(wp + (size_t)kt * kBK);
+  auto gather = [&](int i, bool tv, int ty, int tx, int ch) {
+    const int yy = iy[i] + ty, xx = ix[i] + tx;
+    half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (pv[i] && tv && (unsigned)yy < (unsigned)c.h && (unsigned)xx < (unsigned)c.w)
+      v = *(const half8*)(src + ((int64_t)yy * c.w + xx) * c.src_stride + ch);
+    return v;
   };
-
   floatx4 acc[NT][2];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[t][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-
-  const int nk = a.k_pad / kBK;
-  gload(0);
-  for (int kt = 0; kt < nk; ++kt) {
-    *(half8*)&Xs[srow * kRow + kc * 8] = xr[0];
-    *(half8*)&Xs[(srow + 64) * kRow + kc * 8] = xr[1];
-    if (wv) *(half8*)&Ws[srow * kRow + kc * 8] = wr;
-    __syncthreads();
-    if (kt + 1 < nk) {
-      ch += kBK;
-      while (ch >= c.cin) {
-        ch -= c.cin;
-        ++tap;
-      }
-      gload(kt + 1);
-    }
-    half8 bf[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) bf[j] = *(const half8*)&Xs[(wave * 32 + j * 16 + (lane & 15)) * kRow + (lane >> 4) * 8];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const half8 af = *(const half8*)&Ws[(t * 16 + (lane & 15)) * kRow + (lane >> 4) * 8];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[j], acc[t][j], 0, 0, 0);
-    }
-    __syncthreads();
-  }
+  conv_mma_mainloop<KS, BN>(Xs, Ws, (const half_t*)c.weight, n0, a.k_pad, c.cin, gather, acc);
 
   // acc[t][j][r] is output channel n0 + 16 t + 4 (lane >> 4) + r of pixel m0 + 32 wave + 16 j + (lane & 15) of this image
   bool valid[2];
@@ -148,24 +94,7 @@ __global__ void __launch_bounds__(kThreads) resnet_conv_kernel(const ConvArgs a)
         }
     }
     __syncthreads();
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int n = t * 16 + (lane >> 4) * 4 + r;
-        const float sh = shift[n >> a.cshift];
-        const float d0 = valid[0] ? acc[t][0][r] - sh : 0.f, d1 = valid[1] ? acc[t][1][r] - sh : 0.f;
-        float s1 = d0 + d1, s2 = d0 * d0 + d1 * d1;
-#pragma unroll
-        for (int d = 1; d < 16; d <<= 1) {
-          s1 += __shfl_xor(s1, d);
-          s2 += __shfl_xor(s2, d);
-        }
-        if ((lane & 15) == 0) {
-          red[0][wave][n] = s1;
-          red[1][wave][n] = s2;
-        }
-      }
+    tile_shifted_sums<BN>(acc, valid, [&](int n) { return shift[n >> a.cshift]; }, red);
     __syncthreads();
     if (tid < (BN >> a.cshift)) {
       const int cpg = 1 << a.cshift;
@@ -192,24 +121,7 @@ __global__ void __launch_bounds__(kThreads) resnet_conv_kernel(const ConvArgs a)
       if (c.act == SGR_RESNET_ACT_RELU)
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-      switch (c.out_kind) {
-        case SGR_UPDATE_OUT_CL_F16: {
-          half4 o;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) o[r] = (half_t)v[r];
-          *(half4*)&((half_t*)c.out)[gm[j] * c.out_stride + nb] = o;
-          break;
-        }
-        case SGR_UPDATE_OUT_CL_F32: *(floatx4*)&((float*)c.out)[gm[j] * c.out_stride + nb] = v; break;
-        case SGR_UPDATE_OUT_NCHW_F16:
-#pragma unroll
-          for (int r = 0; r < 4; ++r) ((half_t*)c.out)[((int64_t)img * c.cout + nb + r) * a.HWo + p] = (half_t)v[r];
-          break;
-        default:
-#pragma unroll
-          for (int r = 0; r < 4; ++r) ((float*)c.out)[((int64_t)img * c.cout + nb + r) * a.HWo + p] = v[r];
-          break;
-      }
+      store_out4(c.out, c.out_kind, c.out_stride, v, gm[j], img, p, nb, c.cout, a.HWo);
     }
   }
 }
@@ -248,42 +160,14 @@ struct NormArgs {
   int HW, tiles, C, G, cshift, relu, res_stride, out_stride, pixels;
 };
 
-// The second launch of a norm, grid (pixel blocks, images).  Every workgroup first merges the per-tile statistics of its image in fp64
-// about s0, the reference value of tile 0: with d = s_i - s0, A = sum (n_i d + S1_i) and B = sum (S2_i + 2 d S1_i + n_i d^2) are the
-// sums of (v - s0) and (v - s0)^2 over the group, so mean = s0 + A / N and M2 = B - A^2 / N.  Thread (slot, group) takes the tiles slot,
-// slot + S, ... (S = 256 / groups) in ascending order, the slots are then added in ascending order: the result depends on the map alone.
-// mean and 1 / sqrt(M2 / N + eps) are rounded once to fp32; then y = (v - mean) * rstd * gamma + beta, + residual, ReLU in fp32, one
+// The second launch of a norm, grid (pixel blocks, images).  Every workgroup first merges the per-tile statistics of its image, one
+// statistic per group (merge_tile_stats, sgr_conv_mma.h); then y = (v - mean) * rstd * gamma + beta, + residual, ReLU in fp32, one
 // rounding to fp16.  One thread per (pixel, 8 channels).
 __global__ void __launch_bounds__(kThreads) resnet_norm_kernel(const NormArgs a) {
   __shared__ double pa[kThreads], pb[kThreads];
   __shared__ float mu[kMaxGroups], rs[kMaxGroups];
   const int tid = threadIdx.x, img = blockIdx.y, C = a.C, G = a.G;
-  {
-    const int g = tid % G, slot = tid / G, S = kThreads / G;
-    const floatx4* st = (const floatx4*)a.stats + (int64_t)img * a.tiles * G;
-    const double s0 = (double)st[g][1];
-    double A = 0.0, B = 0.0;
-    if (slot < S)
-      for (int t = slot; t < a.tiles; t += S) {
-        const floatx4 q = st[(int64_t)t * G + g];
-        const double n = q[0], d = (double)q[1] - s0, s1 = q[2], s2 = q[3];
-        A += n * d + s1;
-        B += s2 + 2.0 * d * s1 + n * d * d;
-      }
-    pa[tid] = A;
-    pb[tid] = B;
-    __syncthreads();
-    if (tid < G) {
-      for (int s = 1; s < S; ++s) {
-        A += pa[s * G + tid];
-        B += pb[s * G + tid];
-      }
-      const double N = (double)a.HW * (double)(1 << a.cshift), mean = s0 + A / N, var = fmax((B - A * A / N) / N, 0.0);
-      mu[tid] = (float)mean;
-      rs[tid] = (float)(1.0 / sqrt(var + (double)kEps));
-    }
-    __syncthreads();
-  }
+  merge_tile_stats((const floatx4*)a.stats + (int64_t)img * a.tiles * G, a.tiles, G, (double)a.HW * (double)(1 << a.cshift), pa, pb, mu, rs);
   const int chunks = C / 8, p0 = blockIdx.x * a.pixels;
   for (int i = tid; i < a.pixels * chunks; i += kThreads) {
     const int p = p0 + i / chunks, j = i % chunks;
@@ -341,16 +225,10 @@ __global__ void __launch_bounds__(kThreads) resnet_pool_kernel(const PoolArgs a)
   *(half8*)&a.dst[q * ((int64_t)a.chunks * 8) + j * 8] = best;
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-inline int tiles_of(int64_t hw) { return (int)((hw + kBM - 1) / kBM); }
 inline int pad_before(int i, int k, int s) {            // TF "same": the smaller half of the total goes in front
   const int total = ((i + s - 1) / s - 1) * s + k - i;
   return total > 0 ? total / 2 : 0;
 }
-
-bool map_ok(int n, int h, int w) { return n >= 1 && n <= 65535 && h >= 1 && w >= 1 && (int64_t)h * w <= 0x7fffffff - kBM; }
 
 // log2 of the channels per group, or -1: groups must divide C into a power of two of at most 64 channels, with at most 256 groups
 int group_shift(int C, int groups) {
@@ -417,21 +295,9 @@ int launch_conv(const SgrResnetConv& c, hipStream_t stream) {
   // the widest channel tile that divides cout; a group (a power of two <= 64 that divides cout) then never spans two tiles
   const int bn = c.cout % 64 == 0 ? 64 : c.cout % 32 == 0 ? 32 : 16;
   const dim3 grid((unsigned)a.tiles, (unsigned)(c.cout / bn), (unsigned)c.n), block(kThreads);
-#define SGR_RESNET_LAUNCH(KS)                                                                   \
-  if (bn == 64)                                                                                 \
-    hipLaunchKernelGGL((resnet_conv_kernel<KS, 64>), grid, block, 0, stream, a);                \
-  else if (bn == 32)                                                                            \
-    hipLaunchKernelGGL((resnet_conv_kernel<KS, 32>), grid, block, 0, stream, a);                \
-  else                                                                                          \
-    hipLaunchKernelGGL((resnet_conv_kernel<KS, 16>), grid, block, 0, stream, a)
-  if (c.ksize == 1) {
-    SGR_RESNET_LAUNCH(1);
-  } else if (c.ksize == 3) {
-    SGR_RESNET_LAUNCH(3);
-  } else {
-    SGR_RESNET_LAUNCH(7);
-  }
-#undef SGR_RESNET_LAUNCH
+  dispatch_conv<16, 32, 64>(c.ksize, bn, [&](auto ks, auto bnc) {
+    hipLaunchKernelGGL((resnet_conv_kernel<decltype(ks)::value, decltype(bnc)::value>), grid, block, 0, stream, a);
+  });
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "resnet_conv launch failed");
 }
 
@@ -497,12 +363,7 @@ struct Plan {
 };
 Plan carve(void* base, int n, int H, int W, int stem, const int* chs) {
   Plan s;
-  size_t off = 0;
-  auto take = [&](size_t nbytes) {
-    void* p = base ? (char*)base + off : nullptr;
-    off += align256(nbytes);
-    return p;
-  };
+  Carver cv{base};
   // (pixels, widest map) per level: the stem at 1/2; the pool, stage 0 and the first convolution of stage 1 at 1/4; and so on
   const int64_t hw[4] = {(int64_t)(H / 2) * (W / 2), (int64_t)(H / 4) * (W / 4), (int64_t)(H / 8) * (W / 8), (int64_t)(H / 16) * (W / 16)};
   auto mx = [](int64_t x, int64_t y) { return x > y ? x : y; };
@@ -515,11 +376,11 @@ Plan carve(void* base, int n, int H, int W, int stem, const int* chs) {
     s.stats_elems = s.stats_elems > st ? s.stats_elems : st;
   }
   s.raw_elems = act_elems;
-  s.xin = (half_t*)take((size_t)n * H * W * kInPad * 2);
-  for (int i = 0; i < 4; ++i) s.act[i] = (half_t*)take((size_t)act_elems * 2);
-  s.raw = (float*)take((size_t)s.raw_elems * 4);
-  s.stats = (float*)take((size_t)s.stats_elems * 4);
-  s.bytes = off;
+  s.xin = (half_t*)cv.take((size_t)n * H * W * kInPad * 2);
+  for (int i = 0; i < 4; ++i) s.act[i] = (half_t*)cv.take((size_t)act_elems * 2);
+  s.raw = (float*)cv.take((size_t)s.raw_elems * 4);
+  s.stats = (float*)cv.take((size_t)s.stats_elems * 4);
+  s.bytes = cv.off;
   return s;
 }
 

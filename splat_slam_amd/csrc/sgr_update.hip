@@ -3,27 +3,18 @@
 //   sgr_update_pack      NCHW (fp16 or fp32, any strides) -> channels-last fp16 [pixel][channel], channels zero-padded to a multiple of 8
 //   sgr_update_conv      one implicit-GEMM convolution (1x1, 3x3, 7x7; zero padding, stride 1) on mfma_f32_16x16x32_f16 with a fused epilogue
 //   sgr_update_forward   the whole operator: 17 stream-ordered launches, no host synchronisation
-// Layouts, the launch list and the rounding points are described in DESIGN.md section 3, "Update operator".  The GEMM is
-// D[n][m] = sum_k W[n][k] X[m][k] with m = (edge, y, x) a pixel, n an output channel and k = tap * cin + channel: the weights are the
-// A operand and the pixels the B operand, so that a lane of the accumulator holds four consecutive output channels of one pixel.
-// Every sum has a fixed order (the MFMA k order, serial loops elsewhere): no atomics, bitwise reproducible.
+// Layouts, the launch list and the rounding points are described in DESIGN.md section 3, "Update operator".  The GEMM, its
+// operand roles and the accumulator's lane map are those of sgr_conv_mma.h, shared with the encoders and the ResNet; here a pixel is
+// m = (edge, y, x).  Every sum has a fixed order (the MFMA k order, serial loops elsewhere): no atomics, bitwise reproducible.
 #include <cstdint>
 
-#include "sgr_common.h"
+#include "sgr_conv_mma.h"
 
 namespace sgr {
 int set_error(int code, const char* fmt, ...);
 
 namespace {
 
-typedef _Float16 half_t;
-typedef __attribute__((ext_vector_type(8))) _Float16 half8;
-typedef __attribute__((ext_vector_type(4))) float floatx4;
-
-constexpr int kThreads = 256;
-constexpr int kBM = 128;                    // pixels of one workgroup: 4 waves x 2 tiles of 16
-constexpr int kBK = 32;                     // one MFMA k step
-constexpr int kRow = kBK + 8;               // halfs per LDS row: 80 bytes, so that the 16 rows of a fragment read spread over the banks
 constexpr int kNPad = 64;                   // packed weights have their rows padded to a multiple of this
 constexpr int kHidden = 128;
 constexpr int kCat = 448;                   // [net | inp | corr_enc | flow_enc]
@@ -38,9 +29,8 @@ struct ConvArgs {
 
 __device__ __forceinline__ float sigmoidf(float v) { return 1.f / (1.f + expf(-v)); }
 
-// One workgroup: kBM pixels x BN output channels.  Wave v owns pixels [32v, 32v + 32) as two 16-wide B tiles and all BN / 16 A tiles.
-// Staging: thread t loads the 16-byte chunk k = 8 (t & 3) of pixel rows t >> 2 and 64 + (t >> 2) and of weight row t >> 2 into
-// registers one k step ahead of the MFMAs that consume the previous step out of LDS.
+// The shared tile (sgr_conv_mma.h) on pixels m = (edge, y, x) over all edges: a workgroup's 128 pixels may belong to several edges, the
+// halo test is on (y, x) of each pixel's own map, and the channels come from two sources split at c.split.
 template <int KS, int BN>
 __global__ void __launch_bounds__(kThreads) conv_kernel(const ConvArgs a) {
   constexpr int NT = BN / 16;
@@ -49,7 +39,6 @@ __global__ void __launch_bounds__(kThreads) conv_kernel(const ConvArgs a) {
   const SgrUpdateConv& c = a.c;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int m0 = blockIdx.x * kBM, n0 = blockIdx.y * BN;
-  const int kc = tid & 3, srow = tid >> 2;
   const half_t* src0 = (const half_t*)c.src0;
   const half_t* src1 = (const half_t*)c.src1;
 
@@ -57,67 +46,25 @@ __global__ void __launch_bounds__(kThreads) conv_kernel(const ConvArgs a) {
   bool pv[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    const int m = m0 + srow + 64 * i;
+    const int m = m0 + (tid >> 2) + 64 * i;
     pv[i] = m < a.M;
     pm[i] = pv[i] ? m : 0;
     const int rem = pm[i] % a.HW;
     py[i] = rem / c.w;
     px[i] = rem - py[i] * c.w;
   }
-  const bool wv = tid < BN * 4;
-  const half_t* wp = (const half_t*)c.weight + (size_t)(n0 + (wv ? srow : 0)) * a.k_pad + kc * 8;
-
-  int tap = (kc * 8) / c.cin, ch = (kc * 8) % c.cin;       // this thread's chunk of the current k step
-  half8 xr[2], wr;
-  auto gload = [&](int kt) {
-    const int dy = tap / KS - KS / 2, dx = tap % KS - KS / 2;
-    const bool tv = tap < KS * KS;                           // the zero tail of a k_pad that is no multiple of the taps
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int yy = py[i] + dy, xx = px[i] + dx;
-      half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (pv[i] && tv && (unsigned)yy < (unsigned)c.h && (unsigned)xx < (unsigned)c.w) {   // the halo test is on (y, x) of this pixel
-        const int64_t pix = (int64_t)pm[i] + dy * c.w + dx;                                 // same edge: yy, xx are inside its map
-        const half_t* s = ch < c.split ? src0 + pix * c.stride0 + ch : src1 + pix * c.stride1 + (ch - c.split);
-        v = *(const half8*)s;
-      }
-      xr[i] = v;
+  auto gather = [&](int i, bool tv, int ty, int tx, int ch) {
+    const int dy = ty - KS / 2, dx = tx - KS / 2, yy = py[i] + dy, xx = px[i] + dx;
+    half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (pv[i] && tv && (unsigned)yy < (unsigned)c.h && (unsigned)xx < (unsigned)c.w) {   // the halo test is on (y, x) of this pixel
+      const int64_t pix = (int64_t)pm[i] + dy * c.w + dx;                                 // same edge: yy, xx are inside its map
+      const half_t* s = ch < c.split ? src0 + pix * c.stride0 + ch : src1 + pix * c.stride1 + (ch - c.split);
+      v = *(const half8*)s;
     }
-    if (wv) wr = *(const half8*)(wp + (size_t)kt * kBK);
+    return v;
   };
-
   floatx4 acc[NT][2];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc[t][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-
-  const int nk = a.k_pad / kBK;
-  gload(0);
-  for (int kt = 0; kt < nk; ++kt) {
-    *(half8*)&Xs[srow * kRow + kc * 8] = xr[0];
-    *(half8*)&Xs[(srow + 64) * kRow + kc * 8] = xr[1];
-    if (wv) *(half8*)&Ws[srow * kRow + kc * 8] = wr;
-    __syncthreads();
-    if (kt + 1 < nk) {
-      ch += kBK;
-      while (ch >= c.cin) {
-        ch -= c.cin;
-        ++tap;
-      }
-      gload(kt + 1);
-    }
-    half8 bf[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) bf[j] = *(const half8*)&Xs[(wave * 32 + j * 16 + (lane & 15)) * kRow + (lane >> 4) * 8];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const half8 af = *(const half8*)&Ws[(t * 16 + (lane & 15)) * kRow + (lane >> 4) * 8];
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[j], acc[t][j], 0, 0, 0);
-    }
-    __syncthreads();
-  }
+  conv_mma_mainloop<KS, BN>(Xs, Ws, (const half_t*)c.weight, n0, a.k_pad, c.cin, gather, acc);
 
   // epilogue: acc[t][j][r] is output channel n0 + 16 t + 4 (lane >> 4) + r of pixel m0 + 32 wave + 16 j + (lane & 15)
   const half_t* aux0 = (const half_t*)c.aux0;
@@ -245,10 +192,6 @@ __global__ void __launch_bounds__(kThreads) segmean_kernel(const half_t* __restr
   *(half8*)&out[kp * kHidden + cc * 8] = v;
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 int launch_conv(const SgrUpdateConv& c, hipStream_t stream) {
   if (!c.src0 || !c.weight || !c.bias || !c.out) return set_error(SGR_ERR_INVALID, "update_conv: null argument");
   if (c.E < 1 || c.h < 1 || c.w < 1 || c.cout < 1 || c.cin < 8 || c.cin % 8)
@@ -290,19 +233,9 @@ int launch_conv(const SgrUpdateConv& c, hipStream_t stream) {
   a.k_pad = k_pad;
   const bool narrow = c.cout <= 16;
   const dim3 grid((unsigned)((M + kBM - 1) / kBM), (unsigned)((c.cout + (narrow ? 16 : 64) - 1) / (narrow ? 16 : 64))), block(kThreads);
-#define SGR_UPDATE_LAUNCH(KS)                                                                   \
-  if (narrow)                                                                                   \
-    hipLaunchKernelGGL((conv_kernel<KS, 16>), grid, block, 0, stream, a);                       \
-  else                                                                                          \
-    hipLaunchKernelGGL((conv_kernel<KS, 64>), grid, block, 0, stream, a)
-  if (c.ksize == 1) {
-    SGR_UPDATE_LAUNCH(1);
-  } else if (c.ksize == 3) {
-    SGR_UPDATE_LAUNCH(3);
-  } else {
-    SGR_UPDATE_LAUNCH(7);
-  }
-#undef SGR_UPDATE_LAUNCH
+  dispatch_conv<16, 64>(c.ksize, narrow ? 16 : 64, [&](auto ks, auto bn) {
+    hipLaunchKernelGGL((conv_kernel<decltype(ks)::value, decltype(bn)::value>), grid, block, 0, stream, a);
+  });
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "update_conv launch failed");
 }
 
@@ -322,22 +255,17 @@ struct Scratch {
 };
 Scratch carve(void* base, int64_t M, int64_t MK, int E) {
   Scratch s;
-  size_t off = 0;
-  auto take = [&](size_t nbytes) {
-    void* p = base ? (char*)base + off : nullptr;
-    off += align256(nbytes);
-    return p;
-  };
-  s.cat = (half_t*)take((size_t)M * kCat * 2);
-  s.corr = (half_t*)take((size_t)M * kCorrPad * 2);
-  s.flow = (half_t*)take((size_t)M * kFlowPad * 2);
-  s.tmp = (half_t*)take((size_t)M * kHidden * 2);
-  s.hid2 = (half_t*)take((size_t)M * 2 * kHidden * 2);
-  s.netn = (half_t*)take((size_t)M * kHidden * 2);
-  s.agg = (half_t*)take((size_t)MK * kHidden * 2);
-  s.agg2 = (half_t*)take((size_t)MK * kHidden * 2);
-  s.glo = (float*)take((size_t)E * kGlo * 4);
-  s.bytes = off;
+  Carver cv{base};
+  s.cat = (half_t*)cv.take((size_t)M * kCat * 2);
+  s.corr = (half_t*)cv.take((size_t)M * kCorrPad * 2);
+  s.flow = (half_t*)cv.take((size_t)M * kFlowPad * 2);
+  s.tmp = (half_t*)cv.take((size_t)M * kHidden * 2);
+  s.hid2 = (half_t*)cv.take((size_t)M * 2 * kHidden * 2);
+  s.netn = (half_t*)cv.take((size_t)M * kHidden * 2);
+  s.agg = (half_t*)cv.take((size_t)MK * kHidden * 2);
+  s.agg2 = (half_t*)cv.take((size_t)MK * kHidden * 2);
+  s.glo = (float*)cv.take((size_t)E * kGlo * 4);
+  s.bytes = cv.off;
   return s;
 }
 

@@ -10,24 +10,19 @@
 // a row never sees another row.
 #include <cstdint>
 
-#include "sgr_common.h"
+#include "sgr_conv_mma.h"                   // the vector types and the host helpers; the GEMM here has its own tile
 
 namespace sgr {
 int set_error(int code, const char* fmt, ...);
 
 namespace {
 
-typedef _Float16 half_t;
-typedef __attribute__((ext_vector_type(8))) _Float16 half8;
-typedef __attribute__((ext_vector_type(4))) _Float16 half4;
-typedef __attribute__((ext_vector_type(4))) float floatx4;
 typedef short short4v __attribute__((__vector_size__(8)));
 
-constexpr int kThreads = 256;
 constexpr int kHead = 64;                   // head dimension
 constexpr int kMaxHeads = 16;
 constexpr int kBN = 64;                     // output channels of one GEMM workgroup
-constexpr int kBK = 64;                     // k of one staging step: two MFMA k steps
+constexpr int kBK = 64;                     // k of one staging step: two MFMA k steps (this file's, not the convolution tile's 32)
 constexpr int kRow = kBK + 8;               // halfs per LDS row: 144 bytes, so that the 16 rows of a fragment read spread over the banks
 
 // exact GELU, 0.5 v (1 + erf(v / sqrt 2)), written with erfc so that the left tail keeps its relative accuracy
@@ -311,8 +306,6 @@ __global__ void __launch_bounds__(kThreads) attention_kernel(const half_t* __res
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------------
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 constexpr int64_t kMaxRows = 0x7fffffff - 128;
 
 bool geometry_ok(int64_t B, int64_t T, int heads, int depth) {
@@ -374,21 +367,16 @@ struct Scratch {
 };
 Scratch carve(void* base, int64_t B, int64_t M, int64_t D) {
   Scratch s;
-  size_t off = 0;
-  auto take = [&](size_t nbytes) {
-    void* p = base ? (char*)base + off : nullptr;
-    off += align256(nbytes);
-    return p;
-  };
-  s.stream = (float*)take((size_t)M * D * 4);
-  s.xn = (half_t*)take((size_t)M * D * 2);
-  s.qkv = (half_t*)take((size_t)M * 3 * D * 2);
-  s.att = (half_t*)take((size_t)M * D * 2);
-  s.hid = (half_t*)take((size_t)M * 4 * D * 2);
-  s.tap[0] = (half_t*)take((size_t)M * D * 2);
-  s.tap[1] = (half_t*)take((size_t)M * D * 2);
-  s.rv = (float*)take((size_t)2 * B * D * 4);
-  s.bytes = off;
+  Carver cv{base};
+  s.stream = (float*)cv.take((size_t)M * D * 4);
+  s.xn = (half_t*)cv.take((size_t)M * D * 2);
+  s.qkv = (half_t*)cv.take((size_t)M * 3 * D * 2);
+  s.att = (half_t*)cv.take((size_t)M * D * 2);
+  s.hid = (half_t*)cv.take((size_t)M * 4 * D * 2);
+  s.tap[0] = (half_t*)cv.take((size_t)M * D * 2);
+  s.tap[1] = (half_t*)cv.take((size_t)M * D * 2);
+  s.rv = (float*)cv.take((size_t)2 * B * D * 4);
+  s.bytes = cv.off;
   return s;
 }
 

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from splat_slam_amd import _native as nat
-from splat_slam_amd.update_op import _hash_uniform, _round_up, _stream, _tensor_desc
+from splat_slam_amd._nn_common import ScratchCache, hash_uniform, pack_bias, pack_weight, round_up, stream, tensor_desc
 
 __all__ = ["Encoder", "synthetic_encoder_state_dict", "normalize_encoder_state_dict", "conv2d_f16", "ENCODER_LAYERS", "LAYER_SHAPES",
            "LAUNCH_NAMES", "OUT_DIM", "NORM"]
@@ -85,7 +85,7 @@ def synthetic_encoder_state_dict(which, seed):
         _, cin, k, _ = ENCODER_LAYERS[key.rsplit(".", 1)[0]]
         fan_in = cin * k * k
         scale = math.sqrt(3.0 / fan_in) if key.endswith(".weight") else 1.0 / math.sqrt(fan_in)
-        v = _hash_uniform(which + "." + key, int(np.prod(shape)), seed) * scale
+        v = hash_uniform(which + "." + key, int(np.prod(shape)), seed) * scale
         sd[key] = torch.from_numpy(v.astype(np.float32).reshape(shape))
     return sd
 
@@ -114,23 +114,6 @@ def normalize_encoder_state_dict(sd, which):
     missing = [k for k in shapes if k not in out]
     if missing:
         raise ValueError(f"encoder {which}: the state dict lacks {missing}")
-    return out
-
-
-def _pack_weight(w, cin_pad):
-    """[cout, cin, k, k] -> fp16 [cout][round_up(k*k*cin_pad, 32)], column tap * cin_pad + channel, zero padding"""
-    cout, cin, k, _ = w.shape
-    p = torch.zeros((cout, k * k, cin_pad), dtype=torch.float16, device=w.device)
-    p[:, :, :cin] = w.permute(0, 2, 3, 1).reshape(cout, k * k, cin).to(torch.float16)
-    out = torch.zeros((cout, _round_up(k * k * cin_pad, 32)), dtype=torch.float16, device=w.device)
-    out[:, :k * k * cin_pad] = p.reshape(cout, -1)
-    return out.contiguous()
-
-
-def _pack_bias(b, cout, device):
-    out = torch.zeros(cout, dtype=torch.float32, device=device)
-    if b is not None:
-        out.copy_(b.to(torch.float16).to(torch.float32))
     return out
 
 
@@ -184,10 +167,10 @@ def conv2d_f16(x, w, b=None, stride=1, norm=None, act="none", residual=None, out
     if normed and cout > 128:
         raise RuntimeError(f"{what}: a normalised convolution has cout <= 128, got {cout}")
     dev = x.device
-    cin_pad = _round_up(cin, 8)
+    cin_pad = round_up(cin, 8)
     lib = nat.lib()
     c = nat.SgrEncoderConv()
-    wp, bp = _pack_weight(w, cin_pad), _pack_bias(b, cout, dev)
+    wp, bp = pack_weight(w, cin_pad), pack_bias(b, cout, dev)
     keep = [wp, bp]
     xs = torch.empty((B * h * wd, cin_pad), dtype=torch.float16, device=dev)
     c.src, c.src_stride, c.cin, c.ksize, c.stride, c.n, c.h, c.w = xs.data_ptr(), cin_pad, cin_pad, k, stride, B, h, wd
@@ -215,12 +198,12 @@ def conv2d_f16(x, w, b=None, stride=1, norm=None, act="none", residual=None, out
         c.out = out.data_ptr()
         c.out_kind = nat.SGR_UPDATE_OUT_NCHW_F16 if out_dtype == torch.float16 else nat.SGR_UPDATE_OUT_NCHW_F32
     with torch.cuda.device(dev):
-        desc = _tensor_desc(x)
+        desc = tensor_desc(x)
         if cin == 3:                        # the image pack of the encoders
-            nat.check(lib.sgr_encoder_pack(C.byref(desc), B, h, wd, None, None, xs.data_ptr(), _stream(dev)), "sgr_encoder_pack")
+            nat.check(lib.sgr_encoder_pack(C.byref(desc), B, h, wd, None, None, xs.data_ptr(), stream(dev)), "sgr_encoder_pack")
         else:
-            nat.check(lib.sgr_update_pack(C.byref(desc), B, cin, h, wd, xs.data_ptr(), cin_pad, cin_pad, _stream(dev)), "sgr_update_pack")
-        nat.check(lib.sgr_encoder_conv(C.byref(c), _stream(dev)), "sgr_encoder_conv")
+            nat.check(lib.sgr_update_pack(C.byref(desc), B, cin, h, wd, xs.data_ptr(), cin_pad, cin_pad, stream(dev)), "sgr_update_pack")
+        nat.check(lib.sgr_encoder_conv(C.byref(c), stream(dev)), "sgr_encoder_conv")
     return out.contiguous() if normed else out
 
 
@@ -240,13 +223,13 @@ class Encoder:
         self._weights.norm = nat.SGR_ENCODER_NORM_INSTANCE if self.norm == "instance" else nat.SGR_ENCODER_NORM_NONE
         for i, (name, (_, cin, _, _)) in enumerate(ENCODER_LAYERS.items()):
             w, b = sd[name + ".weight"], sd[name + ".bias"]
-            wp = _pack_weight(w, _round_up(cin, 8)).to(self.device)
-            bp = _pack_bias(b, w.shape[0], "cpu").to(self.device)
+            wp = pack_weight(w, round_up(cin, 8)).to(self.device)
+            bp = pack_bias(b, w.shape[0], "cpu").to(self.device)
             self._keep += [wp, bp]
             self._weights.layer[i].weight, self._weights.layer[i].weight_elems = wp.data_ptr(), wp.numel()
             self._weights.layer[i].bias = bp.data_ptr()
         self.launches = len(LAUNCH_NAMES[which])
-        self._scratch = {}
+        self._scratch = ScratchCache()
 
     @classmethod
     def from_state_dict(cls, sd, which, device="cuda"):
@@ -255,20 +238,6 @@ class Encoder:
     @classmethod
     def synthetic(cls, which, seed, device="cuda"):
         return cls(synthetic_encoder_state_dict(which, seed), which, device)
-
-    def _scratch_for(self, n, H, W, stream):
-        """one buffer per (shape, stream), the four most recent kept"""
-        key = (n, H, W, stream)
-        buf = self._scratch.pop(key, None)
-        if buf is None:
-            nbytes = nat.lib().sgr_encoder_scratch_bytes(n, H, W, self.out_dim, self._weights.norm)
-            if nbytes == 0:
-                raise RuntimeError(f"encoder {self.which}: unsupported sizes (n={n} H={H} W={W})")
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            while len(self._scratch) >= 4:
-                self._scratch.pop(next(iter(self._scratch)))
-        self._scratch[key] = buf
-        return buf
 
     def _prepare(self, images, mean, std, split):
         """checks the arguments, allocates the outputs and fills the call record: (record, outputs)"""
@@ -292,7 +261,7 @@ class Encoder:
             raise RuntimeError(f"{what}: the {H} x {W} image leaves layer3 a {h} x {w} map; an instance norm needs more than one element")
         call = nat.SgrEncoderCall()
         call._images = images.reshape(b * n, 3, H, W)           # a view wherever the strides allow one; kept alive with the record
-        call.images = _tensor_desc(call._images)
+        call.images = tensor_desc(call._images)
         call.n, call.H, call.W = b * n, H, W
         if mean is not None:
             call.normalize = 1
@@ -311,9 +280,12 @@ class Encoder:
     def _run(self, call):
         """enqueues the launches first_launch..last_launch of the record on the current stream"""
         with torch.cuda.device(self.device):
-            stream = _stream(self.device)
-            scratch = self._scratch_for(call.n, call.H, call.W, stream)
-            nat.check(nat.lib().sgr_encoder_forward(C.byref(self._weights), C.byref(call), scratch.data_ptr(), scratch.numel(), stream),
+            st = stream(self.device)
+            n, H, W = call.n, call.H, call.W
+            scratch = self._scratch.get((n, H, W, st), self.device,
+                                        lambda: nat.lib().sgr_encoder_scratch_bytes(n, H, W, self.out_dim, self._weights.norm),
+                                        f"encoder {self.which}: unsupported sizes (n={n} H={H} W={W})")
+            nat.check(nat.lib().sgr_encoder_forward(C.byref(self._weights), C.byref(call), scratch.data_ptr(), scratch.numel(), st),
                       "sgr_encoder_forward")
 
     def __call__(self, images, mean=None, std=None):

@@ -36,7 +36,7 @@ import torch.nn.functional as F
 
 from splat_slam_amd import _native as nat
 from splat_slam_amd import vit as V
-from splat_slam_amd.update_op import _pack_bias, _pack_weight, _round_up, _stream, _tensor_desc
+from splat_slam_amd._nn_common import pack_bias, pack_weight, round_up, stream, tensor_desc
 
 __all__ = ["MonoDepthConfig", "MonoDepth", "check_state_dict", "normalize_state_dict", "synthetic_state_dict", "state_shapes", "same_pad",
            "standardize"]
@@ -185,17 +185,17 @@ class _Conv:
 
     def __init__(self, w, b, device):
         self.cout, self.cin, self.k = w.shape[0], w.shape[1], w.shape[2]
-        self.cin_pad = _round_up(self.cin, 8)
-        self.w = _pack_weight(w.to(device), self.cin_pad)
-        self.b = _pack_bias(None if b is None else b.to(device), self.cout, device)
+        self.cin_pad = round_up(self.cin, 8)
+        self.w = pack_weight(w.to(device), self.cin_pad, 64)
+        self.b = pack_bias(None if b is None else b.to(device), self.cout, device, 64)
 
     def __call__(self, x, act="none", out_dtype=torch.float16):
         B, cin, h, w = x.shape
         dev = x.device
         xs = torch.empty((B * h * w, self.cin_pad), dtype=torch.float16, device=dev)
         with torch.cuda.device(dev):
-            desc = _tensor_desc(x)
-            nat.check(nat.lib().sgr_update_pack(C.byref(desc), B, cin, h, w, xs.data_ptr(), self.cin_pad, self.cin_pad, _stream(dev)),
+            desc = tensor_desc(x)
+            nat.check(nat.lib().sgr_update_pack(C.byref(desc), B, cin, h, w, xs.data_ptr(), self.cin_pad, self.cin_pad, stream(dev)),
                       "sgr_update_pack")
         return self.packed(xs, B, h, w, act, out_dtype)
 
@@ -211,7 +211,7 @@ class _Conv:
         c.out = out.data_ptr()
         c.out_kind = nat.SGR_UPDATE_OUT_NCHW_F16 if out_dtype == torch.float16 else nat.SGR_UPDATE_OUT_NCHW_F32
         with torch.cuda.device(dev):
-            nat.check(nat.lib().sgr_update_conv(C.byref(c), _stream(dev)), "sgr_update_conv")
+            nat.check(nat.lib().sgr_update_conv(C.byref(c), stream(dev)), "sgr_update_conv")
         return out
 
 
@@ -221,7 +221,7 @@ class _DownConv:
     def __init__(self, w16, b16, device):
         from splat_slam_amd.resnetv2 import pack_conv
         self.cout, self.cin = w16.shape[0], w16.shape[1]
-        self.cin_pad = _round_up(self.cin, 8)
+        self.cin_pad = round_up(self.cin, 8)
         self.w = pack_conv(w16.to(device))
         self.b = b16.to(device, torch.float32).contiguous()
 
@@ -238,9 +238,9 @@ class _DownConv:
         c.out, c.out_kind = out.data_ptr(), nat.SGR_UPDATE_OUT_NCHW_F16
         lib = nat.lib()
         with torch.cuda.device(dev):
-            desc = _tensor_desc(x)
-            nat.check(lib.sgr_update_pack(C.byref(desc), B, cin, h, w, xs.data_ptr(), self.cin_pad, self.cin_pad, _stream(dev)), "sgr_update_pack")
-            nat.check(lib.sgr_resnet_conv(C.byref(c), _stream(dev)), "sgr_resnet_conv")
+            desc = tensor_desc(x)
+            nat.check(lib.sgr_update_pack(C.byref(desc), B, cin, h, w, xs.data_ptr(), self.cin_pad, self.cin_pad, stream(dev)), "sgr_update_pack")
+            nat.check(lib.sgr_resnet_conv(C.byref(c), stream(dev)), "sgr_resnet_conv")
         return out
 
 

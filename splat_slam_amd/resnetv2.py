@@ -26,8 +26,7 @@ import torch
 
 from splat_slam_amd import _native as nat
 from splat_slam_amd import mono_depth as M
-from splat_slam_amd.encoder import _pack_weight
-from splat_slam_amd.update_op import _round_up, _stream, _tensor_desc
+from splat_slam_amd._nn_common import ScratchCache, pack_weight, round_up, stream, tensor_desc
 
 __all__ = ["ResNetV2", "LAUNCH_NAMES", "LAYER_NAMES", "backbone_shapes", "normalize_state_dict", "standardized_f16", "pack_conv",
            "conv2d_same_f16", "group_norm_f16", "max_pool_same_f16"]
@@ -100,7 +99,7 @@ def standardized_f16(w):
 def pack_conv(w16):
     """[cout, cin, k, k] -> fp16 [cout][round_up(k * k * cin_pad, 32)], column tap * cin_pad + channel, cin_pad = round_up(cin, 8), zeros
     elsewhere"""
-    return _pack_weight(w16, _round_up(w16.shape[1], 8))
+    return pack_weight(w16, round_up(w16.shape[1], 8))
 
 
 def _gpu(what, name, t, dtypes=(torch.float16, torch.float32)):
@@ -132,8 +131,8 @@ def conv2d_same_f16(x, w, stride=1, padding="same", bias=None, act="none", out_d
         pt = pl = int(padding)
         ho, wo = (h + 2 * pt - k) // stride + 1, (wd + 2 * pl - k) // stride + 1
     dev = x.device
-    cin_pad = _round_up(cin, 8)
-    wp = _pack_weight(w, cin_pad)
+    cin_pad = round_up(cin, 8)
+    wp = pack_weight(w, cin_pad)
     bp = None if bias is None else bias.to(torch.float16).to(torch.float32).contiguous()
     xs = torch.empty((B * h * wd, cin_pad), dtype=torch.float16, device=dev)
     out = torch.empty((B, cout, max(ho, 0), max(wo, 0)), dtype=out_dtype, device=dev)
@@ -145,12 +144,12 @@ def conv2d_same_f16(x, w, stride=1, padding="same", bias=None, act="none", out_d
     c.out_kind = nat.SGR_UPDATE_OUT_NCHW_F16 if out_dtype == torch.float16 else nat.SGR_UPDATE_OUT_NCHW_F32
     lib = nat.lib()
     with torch.cuda.device(dev):
-        desc = _tensor_desc(x)
+        desc = tensor_desc(x)
         if cin == 3:                        # the image pack of the encoders
-            nat.check(lib.sgr_encoder_pack(C.byref(desc), B, h, wd, None, None, xs.data_ptr(), _stream(dev)), "sgr_encoder_pack")
+            nat.check(lib.sgr_encoder_pack(C.byref(desc), B, h, wd, None, None, xs.data_ptr(), stream(dev)), "sgr_encoder_pack")
         else:
-            nat.check(lib.sgr_update_pack(C.byref(desc), B, cin, h, wd, xs.data_ptr(), cin_pad, cin_pad, _stream(dev)), "sgr_update_pack")
-        nat.check(lib.sgr_resnet_conv(C.byref(c), _stream(dev)), "sgr_resnet_conv")
+            nat.check(lib.sgr_update_pack(C.byref(desc), B, cin, h, wd, xs.data_ptr(), cin_pad, cin_pad, stream(dev)), "sgr_update_pack")
+        nat.check(lib.sgr_resnet_conv(C.byref(c), stream(dev)), "sgr_resnet_conv")
     return out
 
 
@@ -177,8 +176,8 @@ def group_norm_f16(x, groups, gamma, beta, relu=False, residual=None):
     g.gamma, g.beta, g.residual, g.residual_stride, g.out, g.out_stride = g32.data_ptr(), b32.data_ptr(), nat.ptr(res), ch, out.data_ptr(), ch
     lib = nat.lib()
     with torch.cuda.device(dev):
-        nat.check(lib.sgr_resnet_stats(raw.data_ptr(), B, h * w, ch, int(groups), stats.data_ptr(), _stream(dev)), "sgr_resnet_stats")
-        nat.check(lib.sgr_resnet_groupnorm(C.byref(g), _stream(dev)), "sgr_resnet_groupnorm")
+        nat.check(lib.sgr_resnet_stats(raw.data_ptr(), B, h * w, ch, int(groups), stats.data_ptr(), stream(dev)), "sgr_resnet_stats")
+        nat.check(lib.sgr_resnet_groupnorm(C.byref(g), stream(dev)), "sgr_resnet_groupnorm")
     return out.permute(0, 3, 1, 2)
 
 
@@ -193,7 +192,7 @@ def max_pool_same_f16(x):
     src = x.permute(0, 2, 3, 1).contiguous()
     out = torch.empty((B, (h + 1) // 2, (w + 1) // 2, ch), dtype=torch.float16, device=x.device)
     with torch.cuda.device(x.device):
-        nat.check(nat.lib().sgr_resnet_maxpool(src.data_ptr(), B, h, w, ch, out.data_ptr(), _stream(x.device)), "sgr_resnet_maxpool")
+        nat.check(nat.lib().sgr_resnet_maxpool(src.data_ptr(), B, h, w, ch, out.data_ptr(), stream(x.device)), "sgr_resnet_maxpool")
     return out.permute(0, 3, 1, 2)
 
 
@@ -221,7 +220,7 @@ class ResNetV2:
         for s in range(3):
             w.stage_chs[s], w.stage_blocks[s] = cfg.stage_chs[s], cfg.stage_layers[s]
         self.launches = len(LAUNCH_NAMES(cfg))
-        self._scratch = {}
+        self._scratch = ScratchCache()
 
     @classmethod
     def from_state_dict(cls, sd, cfg=M.MonoDepthConfig(), device="cuda"):
@@ -231,20 +230,6 @@ class ResNetV2:
     def synthetic(cls, seed, cfg=M.MonoDepthConfig(), device="cuda"):
         shapes = backbone_shapes(_check_cfg(cfg))
         return cls({k: v for k, v in M.synthetic_state_dict(seed, cfg).items() if k in shapes}, cfg, device)
-
-    def _scratch_for(self, n, H, W, stream):
-        """one buffer per (shape, stream), the four most recent kept"""
-        key = (n, H, W, stream)
-        buf = self._scratch.pop(key, None)
-        if buf is None:
-            nbytes = nat.lib().sgr_resnet_scratch_bytes(n, H, W, self.cfg.stem_chs, *self.cfg.stage_chs)
-            if nbytes == 0:
-                raise RuntimeError(f"resnetv2: unsupported sizes (n={n} H={H} W={W})")
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            while len(self._scratch) >= 4:
-                self._scratch.pop(next(iter(self._scratch)))
-        self._scratch[key] = buf
-        return buf
 
     def _prepare(self, x):
         """checks the argument, allocates the outputs and fills the call record: (record, the three [B, h * w, C] buffers)"""
@@ -261,7 +246,7 @@ class ResNetV2:
                      for s, c in zip((2, 3, 4), self.cfg.stage_chs))
         call = nat.SgrResnetCall()
         call._images = x                                        # kept alive with the record
-        call.images = _tensor_desc(x)
+        call.images = tensor_desc(x)
         call.n, call.H, call.W = B, H, W
         call.l1, call.l2, call.l3 = (t.data_ptr() for t in outs)
         call.first_launch, call.last_launch = 0, self.launches - 1
@@ -270,9 +255,12 @@ class ResNetV2:
     def _run(self, call):
         """enqueues the launches first_launch..last_launch of the record on the current stream"""
         with torch.cuda.device(self.device):
-            stream = _stream(self.device)
-            scratch = self._scratch_for(call.n, call.H, call.W, stream)
-            nat.check(nat.lib().sgr_resnet_forward(C.byref(self._weights), C.byref(call), scratch.data_ptr(), scratch.numel(), stream),
+            st = stream(self.device)
+            n, H, W = call.n, call.H, call.W
+            scratch = self._scratch.get((n, H, W, st), self.device,
+                                        lambda: nat.lib().sgr_resnet_scratch_bytes(n, H, W, self.cfg.stem_chs, *self.cfg.stage_chs),
+                                        f"resnetv2: unsupported sizes (n={n} H={H} W={W})")
+            nat.check(nat.lib().sgr_resnet_forward(C.byref(self._weights), C.byref(call), scratch.data_ptr(), scratch.numel(), st),
                       "sgr_resnet_forward")
 
     def channels_last(self, x):

@@ -25,6 +25,8 @@ import numpy as np
 import torch
 
 from splat_slam_amd import _native as nat
+from splat_slam_amd._nn_common import ScratchCache, pack_bias, pack_weight, round_up, stream, tensor_desc
+from splat_slam_amd._nn_common import hash_uniform as _hash_uniform      # its name here before the networks shared it
 
 __all__ = ["UpdateOperator", "synthetic_state_dict", "normalize_state_dict", "conv2d_f16", "LAYER_SHAPES"]
 
@@ -41,26 +43,6 @@ for _n, (_o, _i, _k) in _CONVS.items():
     LAYER_SHAPES[_n + ".weight"] = (_o, _i, _k, _k)
     LAYER_SHAPES[_n + ".bias"] = (_o,)
 _SLICED = ("weight.2", "delta.2")        # checkpoints carry 3 output rows here; the first 2 are used
-
-
-def _name_hash(name):
-    h = 2166136261                        # FNV-1a, 32 bit
-    for b in name.encode():
-        h = ((h ^ b) * 16777619) & 0xFFFFFFFF
-    return h
-
-
-def _hash_uniform(name, n, seed):
-    """n values of U[-1, 1): the murmur3 finaliser of (flat index * 0x9E3779B1 + FNV-1a(name) + seed * 0x85EBCA77) mod 2^32."""
-    m = np.uint64(0xFFFFFFFF)
-    x = (np.arange(n, dtype=np.uint64) * np.uint64(0x9E3779B1) + np.uint64(_name_hash(name))
-         + np.uint64((int(seed) * 0x85EBCA77) & 0xFFFFFFFF)) & m
-    x ^= x >> np.uint64(16)
-    x = (x * np.uint64(0x85EBCA6B)) & m
-    x ^= x >> np.uint64(13)
-    x = (x * np.uint64(0xC2B2AE35)) & m
-    x ^= x >> np.uint64(16)
-    return x.astype(np.float64) / 2.0 ** 31 - 1.0
 
 
 def synthetic_state_dict(seed):
@@ -101,43 +83,6 @@ def normalize_state_dict(sd):
     return out
 
 
-def _round_up(v, m):
-    return (v + m - 1) // m * m
-
-
-def _pack_weight(w, cin_pad):
-    """[cout, cin, k, k] -> fp16 [round_up(cout, 64)][round_up(k*k*cin_pad, 32)], column tap * cin_pad + channel, zero padding"""
-    cout, cin, k, _ = w.shape
-    p = torch.zeros((cout, k * k, cin_pad), dtype=torch.float16, device=w.device)
-    p[:, :, :cin] = w.permute(0, 2, 3, 1).reshape(cout, k * k, cin).to(torch.float16)
-    out = torch.zeros((_round_up(cout, 64), _round_up(k * k * cin_pad, 32)), dtype=torch.float16, device=w.device)
-    out[:cout, :k * k * cin_pad] = p.reshape(cout, -1)
-    return out.contiguous()
-
-
-def _pack_bias(b, cout, device):
-    out = torch.zeros(_round_up(cout, 64), dtype=torch.float32, device=device)
-    if b is not None:
-        out[:cout] = b.to(torch.float16).to(torch.float32)
-    return out
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _tensor_desc(t):
-    """SgrUpdateTensor of a [E,C,h,w] view (None: zeros)"""
-    d = nat.SgrUpdateTensor()
-    if t is None:
-        d.data, d.dtype = None, nat.SGR_UPDATE_F32
-        return d
-    d.data = t.data_ptr()
-    d.stride = (C.c_int64 * 4)(*t.stride())
-    d.dtype = nat.SGR_UPDATE_F16 if t.dtype == torch.float16 else nat.SGR_UPDATE_F32
-    return d
-
-
 def conv2d_f16(x, w, b=None, act="none", out_dtype=torch.float16):
     """act(conv2d(x, w, b)) with zero padding (k - 1) / 2 and stride 1: x [B,cin,h,w] and w [cout,cin,k,k] (k = 1, 3 or 7) are rounded to
     fp16, the sums are fp32, the result [B,cout,h,w] is out_dtype (fp16 or fp32).  act: none, relu, sigmoid, tanh."""
@@ -158,10 +103,10 @@ def conv2d_f16(x, w, b=None, act="none", out_dtype=torch.float16):
     if min(B, cin, h, wd, cout) < 1 or (b is not None and tuple(b.shape) != (cout,)):
         raise RuntimeError(f"update_op.conv2d_f16: empty tensor or a bias that is not [{cout}]")
     dev = x.device
-    cin_pad = _round_up(cin, 8)
+    cin_pad = round_up(cin, 8)
     lib = nat.lib()
     xs = torch.empty((B * h * wd, cin_pad), dtype=torch.float16, device=dev)
-    wp, bp = _pack_weight(w, cin_pad), _pack_bias(b, cout, dev)
+    wp, bp = pack_weight(w, cin_pad, 64), pack_bias(b, cout, dev, 64)
     out = torch.empty((B, cout, h, wd), dtype=out_dtype, device=dev)
     c = nat.SgrUpdateConv()
     c.src0, c.stride0, c.cin, c.ksize, c.E, c.h, c.w = xs.data_ptr(), cin_pad, cin_pad, k, B, h, wd
@@ -169,9 +114,9 @@ def conv2d_f16(x, w, b=None, act="none", out_dtype=torch.float16):
     c.out = out.data_ptr()
     c.out_kind = nat.SGR_UPDATE_OUT_NCHW_F16 if out_dtype == torch.float16 else nat.SGR_UPDATE_OUT_NCHW_F32
     with torch.cuda.device(dev):
-        desc = _tensor_desc(x)
-        nat.check(lib.sgr_update_pack(C.byref(desc), B, cin, h, wd, xs.data_ptr(), cin_pad, cin_pad, _stream(dev)), "sgr_update_pack")
-        nat.check(lib.sgr_update_conv(C.byref(c), _stream(dev)), "sgr_update_conv")
+        desc = tensor_desc(x)
+        nat.check(lib.sgr_update_pack(C.byref(desc), B, cin, h, wd, xs.data_ptr(), cin_pad, cin_pad, stream(dev)), "sgr_update_pack")
+        nat.check(lib.sgr_update_conv(C.byref(c), stream(dev)), "sgr_update_conv")
     return out
 
 
@@ -198,8 +143,8 @@ class UpdateOperator:
         for i, (names, cin_pad) in enumerate(_PACKED):
             w = torch.cat([sd[n + ".weight"] for n in names])
             b = torch.cat([sd[n + ".bias"] for n in names])
-            wp = _pack_weight(w, cin_pad).to(self.device)
-            bp = _pack_bias(b, w.shape[0], "cpu").to(self.device)
+            wp = pack_weight(w, cin_pad, 64).to(self.device)
+            bp = pack_bias(b, w.shape[0], "cpu", 64).to(self.device)
             self._keep += [wp, bp]
             self._weights.layer[i].weight, self._weights.layer[i].weight_elems = wp.data_ptr(), wp.numel()
             self._weights.layer[i].bias = bp.data_ptr()
@@ -208,7 +153,7 @@ class UpdateOperator:
         gw, gb = gw.to(self.device), gb.to(self.device)
         self._keep += [gw, gb]
         self._weights.glo_weight, self._weights.glo_bias = gw.data_ptr(), gb.data_ptr()
-        self._scratch = {}
+        self._scratch = ScratchCache()
 
     @classmethod
     def from_state_dict(cls, sd, device="cuda"):
@@ -217,20 +162,6 @@ class UpdateOperator:
     @classmethod
     def synthetic(cls, seed, device="cuda"):
         return cls(synthetic_state_dict(seed), device)
-
-    def _scratch_for(self, E, K, h, w, stream):
-        """one buffer per (shape, stream), the four most recent kept"""
-        key = (E, K, h, w, stream)
-        buf = self._scratch.pop(key, None)
-        if buf is None:
-            nbytes = nat.lib().sgr_update_scratch_bytes(E, K, h, w)
-            if nbytes == 0:
-                raise RuntimeError(f"update_op: unsupported sizes (E={E} K={K} h={h} w={w})")
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            while len(self._scratch) >= 4:
-                self._scratch.pop(next(iter(self._scratch)))
-        self._scratch[key] = buf
-        return buf
 
     def _check(self, net, inp, corr, flow, ii):
         for name, t, ch in (("net", net, HIDDEN), ("inp", inp, HIDDEN), ("corr", corr, CORR_PLANES), ("flow", flow, FLOW_PLANES)):
@@ -262,8 +193,8 @@ class UpdateOperator:
             uniq, ix = torch.unique(ii.to(dev), sorted=True, return_inverse=True)
             K, ix = uniq.shape[0], ix.contiguous()
         call = nat.SgrUpdateCall()
-        call.net, call.inp, call.corr = _tensor_desc(net[0]), _tensor_desc(inp[0]), _tensor_desc(corr[0])
-        call.flow = _tensor_desc(None if flow is None else flow[0])
+        call.net, call.inp, call.corr = tensor_desc(net[0]), tensor_desc(inp[0]), tensor_desc(corr[0])
+        call.flow = tensor_desc(None if flow is None else flow[0])
         call.E, call.h, call.w, call.K = E, h, w, K
         net_out = torch.empty((1, E, HIDDEN, h, w), dtype=torch.float16, device=dev)
         delta = torch.empty((1, E, h, w, 2), dtype=torch.float16, device=dev)
@@ -281,9 +212,11 @@ class UpdateOperator:
     def _run(self, call):
         """enqueues the launches first_launch..last_launch of the record on the current stream"""
         with torch.cuda.device(self.device):
-            stream = _stream(self.device)
-            scratch = self._scratch_for(call.E, call.K, call.h, call.w, stream)
-            nat.check(nat.lib().sgr_update_forward(C.byref(self._weights), C.byref(call), scratch.data_ptr(), scratch.numel(), stream),
+            st = stream(self.device)
+            E, K, h, w = call.E, call.K, call.h, call.w
+            scratch = self._scratch.get((E, K, h, w, st), self.device, lambda: nat.lib().sgr_update_scratch_bytes(E, K, h, w),
+                                        f"update_op: unsupported sizes (E={E} K={K} h={h} w={w})")
+            nat.check(nat.lib().sgr_update_forward(C.byref(self._weights), C.byref(call), scratch.data_ptr(), scratch.numel(), st),
                       "sgr_update_forward")
 
     def __call__(self, net, inp, corr, flow=None, ii=None, jj=None):

@@ -7,7 +7,7 @@ gfx950 kernels `sgr_vit_*` (include/splat_hip.h, csrc/sgr_vit.hip).  Inference o
     VisionTransformer.synthetic(seed, cfg=VitConfig(), device="cuda")      weights of synthetic_state_dict(seed, cfg)
     vit(patch_features [B,cin,gh,gw]) -> (tap_a, tap_b)                     each fp16 [B,dim,gh,gw]
     vit.tokens(patches [B,gh*gw,cin] fp16, gh, gw) -> (tap_a, tap_b)        the same on channels-last features, without the copy
-    synthetic_state_dict(seed, cfg)      fp32 CPU tensors by the closed-form integer hash of update_op (name, flat index, seed)
+    synthetic_state_dict(seed, cfg)      fp32 CPU tensors by the update operator's closed-form integer hash of (name, flat index, seed)
     normalize_state_dict(sd, cfg)        validation alone (touches no device); state_shapes(cfg) lists the keys
     resize_pos_embed(pos, g0, gh, gw)    the reference's _resize_pos_embed: bilinear, align_corners=False, the class row kept
     layernorm, gemm, attention           the single kernels on torch tensors (what the tests and the timing script call)
@@ -27,7 +27,8 @@ import torch
 import torch.nn.functional as F
 
 from splat_slam_amd import _native as nat
-from splat_slam_amd.update_op import _name_hash
+from splat_slam_amd import _nn_common
+from splat_slam_amd._nn_common import ScratchCache, stream
 
 __all__ = ["VitConfig", "VisionTransformer", "synthetic_state_dict", "normalize_state_dict", "state_shapes", "resize_pos_embed",
            "hash_uniform", "layernorm", "gemm", "attention", "launch_names"]
@@ -72,16 +73,8 @@ def state_shapes(cfg):
 
 
 def hash_uniform(name, n, seed):
-    """update_op._hash_uniform in torch integer arithmetic (int64 wraps as uint64 does, and only the low 32 bits are kept): n values of
-    U[-1, 1) as float64"""
-    m = 0xFFFFFFFF
-    x = (torch.arange(n, dtype=torch.int64) * 0x9E3779B1 + (_name_hash(name) + ((int(seed) * 0x85EBCA77) & m))) & m
-    x = x ^ (x >> 16)
-    x = (x * 0x85EBCA6B) & m
-    x = x ^ (x >> 13)
-    x = (x * 0xC2B2AE35) & m
-    x = x ^ (x >> 16)
-    return x.to(torch.float64) / 2.0 ** 31 - 1.0
+    """n values of U[-1, 1) as a float64 tensor: the closed-form integer hash every synthetic network here draws its weights from"""
+    return torch.from_numpy(_nn_common.hash_uniform(name, n, seed))
 
 
 def synthetic_tensor(key, shape, seed, scale, offset=0.0):
@@ -131,10 +124,6 @@ def launch_names(depth):
     return names + ["readout3.cls", "readout3", "readout4.cls", "readout4"]
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _gpu(name, t, dtype):
     if not isinstance(t, torch.Tensor) or not t.is_cuda:
         raise RuntimeError(f"vit (MI355X build): {name} must be a GPU tensor; there is no CPU path")
@@ -150,7 +139,7 @@ def layernorm(x, gamma, beta):
     M, D = x.shape
     out = torch.empty((M, D), dtype=torch.float16, device=x.device)
     with torch.cuda.device(x.device):
-        nat.check(nat.lib().sgr_vit_layernorm(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), M, D, out.data_ptr(), _stream(x.device)),
+        nat.check(nat.lib().sgr_vit_layernorm(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), M, D, out.data_ptr(), stream(x.device)),
                   "sgr_vit_layernorm")
     return out
 
@@ -185,7 +174,7 @@ def gemm(a, w, bias=None, epi="store_f16", out=None, tap=False, aux=None, T=0):
         raise RuntimeError(f"vit.gemm: unknown epilogue {epi!r}")
     g.out = out.data_ptr()
     with torch.cuda.device(dev):
-        nat.check(nat.lib().sgr_vit_gemm(C.byref(g), _stream(dev)), "sgr_vit_gemm")
+        nat.check(nat.lib().sgr_vit_gemm(C.byref(g), stream(dev)), "sgr_vit_gemm")
     return out if ret is None else ret
 
 
@@ -197,7 +186,7 @@ def attention(qkv):
     B, T, _, heads, _ = qkv.shape
     out = torch.empty((B, T, heads * 64), dtype=torch.float16, device=qkv.device)
     with torch.cuda.device(qkv.device):
-        nat.check(nat.lib().sgr_vit_attention(qkv.data_ptr(), B, T, heads, out.data_ptr(), _stream(qkv.device)), "sgr_vit_attention")
+        nat.check(nat.lib().sgr_vit_attention(qkv.data_ptr(), B, T, heads, out.data_ptr(), stream(qkv.device)), "sgr_vit_attention")
     return out
 
 
@@ -238,7 +227,7 @@ class VisionTransformer:
             w.readout_w[j], w.readout_b[j] = f16(n + ".weight"), f32(n + ".bias")
         self._pos_embed = sd["model.pos_embed"].to(self.device, torch.float32)
         self._cls = sd["model.cls_token"].to(self.device, torch.float32).reshape(1, cfg.dim)
-        self._pos, self._scratch = {}, {}
+        self._pos, self._scratch = {}, ScratchCache()
         self.launches = 5 + 7 * cfg.depth
 
     @classmethod
@@ -257,20 +246,6 @@ class VisionTransformer:
             t[0] += self._cls[0]
             t = self._pos[(gh, gw)] = t.contiguous()
         return t
-
-    def _scratch_for(self, B, T, stream):
-        """one buffer per (shape, stream), the four most recent kept"""
-        key = (B, T, stream)
-        buf = self._scratch.pop(key, None)
-        if buf is None:
-            nbytes = nat.lib().sgr_vit_scratch_bytes(B, T, self.cfg.heads, self.cfg.depth)
-            if nbytes == 0:
-                raise RuntimeError(f"vit: unsupported sizes (B={B} T={T})")
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            while len(self._scratch) >= 4:
-                self._scratch.pop(next(iter(self._scratch)))
-        self._scratch[key] = buf
-        return buf
 
     def _prepare(self, x):
         """checks the argument, allocates the outputs and fills the call record: (record, outputs, tensors the record points into)"""
@@ -295,9 +270,11 @@ class VisionTransformer:
     def _run(self, call):
         """enqueues the launches first_launch..last_launch of the record on the current stream"""
         with torch.cuda.device(self.device):
-            stream = _stream(self.device)
-            scratch = self._scratch_for(call.B, 1 + call.gh * call.gw, stream)
-            nat.check(nat.lib().sgr_vit_forward(C.byref(self._weights), C.byref(call), scratch.data_ptr(), scratch.numel(), stream),
+            st = stream(self.device)
+            B, T = call.B, 1 + call.gh * call.gw
+            scratch = self._scratch.get((B, T, st), self.device, lambda: nat.lib().sgr_vit_scratch_bytes(B, T, self.cfg.heads, self.cfg.depth),
+                                        f"vit: unsupported sizes (B={B} T={T})")
+            nat.check(nat.lib().sgr_vit_forward(C.byref(self._weights), C.byref(call), scratch.data_ptr(), scratch.numel(), st),
                       "sgr_vit_forward")
 
     def __call__(self, patch_features):

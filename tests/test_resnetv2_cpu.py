@@ -1,10 +1,19 @@
 """splat_slam_amd.resnetv2 without a GPU: the weight packing against a numpy gather, the standardised fp16 kernels against
-mono_depth_ref.prepare, the launch list, the scratch size, the state-dict contract and the backbone switch of MonoDepth."""
+mono_depth_ref.prepare, the launch list, the scratch size, the state-dict contract, the backbone switch of MonoDepth and the build of the
+kernels for gfx950."""
+import os
+import re
+import shutil
+import subprocess
+
 import numpy as np
 import pytest
 import torch
 
 import mono_depth_ref as MR
+from conftest import ROOT
+
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def reduced_cfg(**kw):
@@ -116,3 +125,52 @@ def test_an_unknown_backbone_raises_before_any_device_is_touched():
         MonoDepth.synthetic(1, reduced_cfg(), backbone="HIP")
     with pytest.raises(ValueError, match="backbone"):
         MonoDepth.from_state_dict({}, reduced_cfg(), backbone=None)
+
+
+# kernel -> the VGPR count of its gfx950 code object when it was written, as a ceiling
+VGPR_CEILING = {"resnet_conv_kernelILi1ELi16E": 52, "resnet_conv_kernelILi3ELi16E": 52, "resnet_conv_kernelILi7ELi16E": 52,
+                "resnet_conv_kernelILi1ELi32E": 68, "resnet_conv_kernelILi3ELi32E": 64, "resnet_conv_kernelILi7ELi32E": 64,
+                "resnet_conv_kernelILi1ELi64E": 88, "resnet_conv_kernelILi3ELi64E": 88, "resnet_conv_kernelILi7ELi64E": 88,
+                "resnet_norm_kernel": 50, "resnet_stats_kernel": 12, "resnet_pool_kernel": 30}
+
+
+def test_resnet_kernels_compile_for_gfx950_without_scratch(tmp_path):
+    """every kernel keeps its state in registers: no private segment, no spills (read from the code object's metadata)"""
+    if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
+        pytest.skip("hipcc not available")
+    out = str(tmp_path / "resnet.s")
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-S", "--cuda-device-only", "-o", out,
+                    os.path.join(ROOT, "splat_slam_amd", "csrc", "sgr_resnet.hip")], check=True, capture_output=True)
+    text = open(out).read()
+    assert "v_mfma_f32_16x16x32_f16" in text
+    seen = set()
+    for block in text.split("\n  - ")[1:]:
+        name = re.search(r"\.name:\s+(\S+)", block)
+        key = next((k for k in VGPR_CEILING if name and k in name.group(1)), None)
+        if key is None:
+            continue
+        seen.add(key)
+        vgpr = int(re.search(r"\.vgpr_count:\s+(\d+)", block).group(1))
+        spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", block).group(1))
+        scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", block).group(1))
+        print(key, "vgpr", vgpr)
+        assert scratch == 0 and spill == 0 and vgpr <= VGPR_CEILING[key], (key, vgpr, spill, scratch)
+    assert seen == set(VGPR_CEILING)
+
+
+def test_a_group_never_spans_two_channel_tiles():
+    """The convolution folds the per-channel sums red[.][wave][0 .. BN) of its own channel tile into groups, so every group must lie
+    inside one tile.  The launch takes the widest of 64 / 32 / 16 that divides cout; for every (cout, groups) the kernels accept (cout a
+    multiple of 16 up to 1024, at most 256 groups, a power of two of at most 64 channels per group) the group size divides that tile."""
+    checked = 0
+    for cout in range(16, 1025, 16):
+        bn = 64 if cout % 64 == 0 else 32 if cout % 32 == 0 else 16
+        for groups in range(1, 257):
+            cpg = cout // groups
+            if cout % groups or cpg > 64 or cpg & (cpg - 1):
+                continue
+            checked += 1
+            assert bn % cpg == 0, (cout, groups, bn)
+            for g in range(groups):
+                assert g * cpg // bn == ((g + 1) * cpg - 1) // bn, (cout, groups, g)
+    assert checked >= 3 * 64                    # 4, 8 and 16 channels per group fit every one of the 64 widths

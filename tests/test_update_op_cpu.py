@@ -158,7 +158,8 @@ def test_update_kernels_compile_for_gfx950_without_scratch(tmp_path):
         spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", block).group(1))
         scratch = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", block).group(1))
         print(name.group(1), "vgpr", vgpr)
-        assert scratch == 0 and spill == 0 and vgpr <= 128, (name.group(1), vgpr, spill, scratch)
+        ceiling = {"16": 60, "64": 108}[CONV_KERNELS.search(name.group(1)).group(1)]       # BN -> the count when it was written
+        assert scratch == 0 and spill == 0 and vgpr <= ceiling, (name.group(1), vgpr, spill, scratch)
     assert seen == 6
     from splat_slam_amd import _native as nat
     lib = nat.lib()
