@@ -129,10 +129,13 @@ __device__ inline float frame_depth(const FrameDev& f, int o, float depth_trunc)
   return d > depth_trunc ? 0.f : d;
 }
 
-// colour byte of channel c: (clamp(exp(a) r + b, 0, 1) * 255) truncated; rounded at every step (no contraction)
+// colour byte of channel c: (clamp(exp(a) r + b, 0, 1) * 255) truncated; a multiply, an add and a multiply, each rounded on its
+// own: the bits of torch's exp(a) * r + b (the __fmul_rn / __fadd_rn intrinsics do not keep the compiler from fusing them)
 __device__ inline float frame_color(const FrameDev& f, float ea, float eb, int c, size_t HW, int o) {
-  const float img = fminf(fmaxf(__fadd_rn(__fmul_rn(ea, f.render[c * HW + o]), eb), 0.f), 1.f);
-  return (float)(int)__fmul_rn(img, kColorScale);
+#pragma clang fp contract(off)
+  const float scaled = ea * f.render[c * HW + o];
+  const float img = fminf(fmaxf(scaled + eb, 0.f), 1.f);
+  return (float)(int)(img * kColorScale);
 }
 
 // ---- touch: thread = sampled pixel of one frame (grid.y)
@@ -612,6 +615,9 @@ __global__ void __launch_bounds__(kThreads) tri_keep_kernel(int F, const int32_t
   const int a = tris[(size_t)t * 3], b = tris[(size_t)t * 3 + 1], d = tris[(size_t)t * 3 + 2];
   bool keep = c.csize[c.label[a]] >= min_len && a != b && b != d && a != d;
   if (keep) {
+    // every product is rounded on its own: with e1 == e2, or e2 a power of two times e1, the two products of a component are then
+    // the same float and the face is dropped, where an fma would leave the rounding residual of one product
+#pragma clang fp contract(off)
     float e1[3], e2[3];
     for (int k = 0; k < 3; ++k) {
       e1[k] = verts[(size_t)b * 3 + k] - verts[(size_t)a * 3 + k];

@@ -91,6 +91,45 @@ class TSDFVolume:
         self._alloc(cap, max(1, int(pool_capacity)))
         self.reset()
 
+    @classmethod
+    def from_voxels(cls, vox, voxel_length, sdf_trunc, depth_trunc=30.0, device="cuda", hash_capacity=None, pool_capacity=None):
+        """the inverse of voxels(): a volume that holds exactly the units of vox (keys int64 [n,3], tsdf / weight [n,4096], color
+        [n,4096,3] on 0..255; numpy or torch, any device), in a hash of at least 2 n slots and a pool of at least n units.  The keys
+        go into the first n slots of a source state and sgr_tsdf_rehash inserts them: no kernel of its own."""
+        get = lambda name: torch.as_tensor(vox[name]).detach()
+        keys, tsdf, weight, color = get("keys").cpu(), get("tsdf"), get("weight"), get("color")
+        if keys.dim() != 2 or keys.shape[1] != 3 or keys.dtype != torch.int64:
+            raise ValueError(f"TSDFVolume.from_voxels: keys must be int64 [n,3], got {tuple(keys.shape)} {keys.dtype}")
+        n = keys.shape[0]
+        if tuple(tsdf.shape) != (n, 4096) or tuple(weight.shape) != (n, 4096) or tuple(color.shape) != (n, 4096, 3):
+            raise ValueError(f"TSDFVolume.from_voxels: tsdf / weight must be [{n},4096] and color [{n},4096,3], got "
+                             f"{tuple(tsdf.shape)}, {tuple(weight.shape)}, {tuple(color.shape)}")
+        bias = 1 << 20
+        if n and (int(keys.min()) < -bias or int(keys.max()) >= bias):
+            raise ValueError("TSDFVolume.from_voxels: unit keys outside [-2^20, 2^20)")
+        packed = ((keys[:, 0] + bias) << 42) | ((keys[:, 1] + bias) << 21) | (keys[:, 2] + bias)
+        if torch.unique(packed).numel() != n:
+            raise ValueError("TSDFVolume.from_voxels: duplicate unit keys")
+        vol = cls(voxel_length, sdf_trunc, depth_trunc, device, max(int(hash_capacity or 0), 2 * n),
+                  max(int(pool_capacity or 0), n, 1))
+        if n == 0:
+            return vol
+        src_cap = 64
+        while src_cap < n:
+            src_cap *= 2
+        src = torch.zeros(vol._lib.sgr_tsdf_bytes(src_cap), dtype=torch.uint8, device=vol.device)
+        src[:src_cap * 8].fill_(0xFF)
+        src[:n * 8].view(torch.int64).copy_(packed)
+        src[src_cap * 8:src_cap * 8 + n * 4].view(torch.int32).copy_(torch.arange(n, dtype=torch.int32))
+        src[20 * src_cap:20 * src_cap + 4].view(torch.int32).fill_(n)
+        pool = vol._pool.view(-1, 5, 4096)
+        pool[:n, 0].copy_(tsdf.float())
+        pool[:n, 1].copy_(weight.float())
+        pool[:n, 2:5].copy_(color.float().permute(0, 2, 1))
+        nat.check(vol._lib.sgr_tsdf_rehash(vol._vol(state=src, cap=src_cap), vol._vol(), _stream()), "sgr_tsdf_rehash")
+        vol.num_units = n
+        return vol
+
     # ---- state
     def _alloc(self, cap, pool_cap):
         self.hash_capacity, self.pool_capacity = cap, pool_cap
