@@ -1143,6 +1143,66 @@ int sgr_resnet_groupnorm(const SgrResnetNorm* norm, void* stream);
 int sgr_resnet_maxpool(const void* src, int32_t n, int32_t h, int32_t w, int32_t channels, void* dst, void* stream);
 int sgr_resnet_forward(const SgrResnetWeights* weights, const SgrResnetCall* call, void* scratch, size_t scratch_bytes, void* stream);
 
+/* The decoder of the mono-depth prior (reassemble, layerN_rn, four fusion blocks, head) and the two resizes of predict, inference
+ * only.  Stated in DESIGN.md section 3, "DPT decoder".  Everything is stream-ordered, allocates nothing, synchronises nothing, uses no
+ * atomics and is bitwise reproducible; an image gives the same bits alone and inside any batch.  Maps are channels-last fp16
+ * [image][y][x][channel] with a row stride in halfs that is a multiple of 8 and a 16-byte aligned base; n * h * w must fit int32.
+ * sgr_dpt_conv: stride 1, ksize 1 or 3, zero padding (ksize - 1) / 2, cin a multiple of 8 up to 1024, cout 1..1024.  weight is fp16
+ * [round_up(cout, 64)][round_up(ksize^2 * cin, 32)], k = tap * cin + c, padding zero; bias fp32 [round_up(cout, 64)] or NULL.  With
+ * relu_in every input value x is read as max(x, 0).  In fp32: v = sum + bias, with relu v = max(v, 0), then v += res0[m][n] and
+ * v += res1[m][n] (each channels-last fp16 or NULL), one rounding.  out_kind SGR_UPDATE_OUT_CL_F16 (out_stride a multiple of 8) or
+ * SGR_UPDATE_OUT_CL_F32 (any out_stride >= cout; cout = 1, out_stride = 1 is the plane [n][h][w]).  A tile of 128 pixels may span images.
+ * sgr_dpt_up2: bilinear, align_corners = True, [n][h][w][channels] -> [n][2h][2w][channels], channels a multiple of 8; output row o
+ * reads the source position o (h - 1) / (2h - 1), split into integer and fraction in integers; the four weights and the sum are fp32.
+ * sgr_dpt_resize_in: src fp32 [planes][H][W] -> dst fp16 [planes][h][w] = ((antialiased bilinear resize, align_corners = False) - 0.5)
+ * / 0.5: with S = max(in, out) per axis, output o sums the taps x with integer weight max(0, 2S - |(2x + 1) out - (2o + 1) in|),
+ * divided by their sum.
+ * sgr_dpt_resize_out: src fp32 [planes][h][w] -> dst fp32 [planes][H][W] = clamp(bicubic(clamp(src, 0, 1)), 0, 1): cubic convolution with
+ * A = -0.75, align_corners = False, source position ((2o + 1) in - out) / (2 out) from integers, border indices clamped.
+ * sgr_dpt_forward: taps [n,dim,H/16,W/16] (NCHW, any strides), l1 [n][H/4*W/4][chs0] and l2 [n][H/8*W/8][chs1] (the stage maps of
+ * sgr_resnet_forward) -> depth fp32 [n][H][W].  layer[] order: act_postprocess3.3, act_postprocess4.3, act_postprocess4.4 (packed as
+ * for sgr_resnet_conv: [dim] rows, bias fp32 [dim]), layer1_rn .. layer4_rn, refinenet4.{resConfUnit2.conv1, .conv2, out_conv}, for
+ * i = 3, 2, 1 refinenet{i}.{resConfUnit1.conv1, .conv2, resConfUnit2.conv1, .conv2, out_conv}, output_conv.0, .2, .4.  The 35
+ * launches: pack3, act_postprocess3.3, pack4, act_postprocess4.3, act_postprocess4.4 (sgr_resnet_conv, stride 2), the four layerN_rn,
+ * per fusion block its convolutions (the adds in the epilogues), up2 and out_conv, then output_conv.0, up2, output_conv.2 (ReLU),
+ * output_conv.4 (ReLU, fp32); first_launch <= i <= last_launch are enqueued.  dim and features are multiples of 16 up to 1024, H and W
+ * multiples of 32.  scratch: sgr_dpt_scratch_bytes(n, H, W, dim, features) bytes, 16-byte aligned (0 = unsupported sizes). */
+#define SGR_DPT_LAYERS 28
+#define SGR_DPT_LAUNCHES 35
+typedef struct SgrDptConv {
+  const void* src;
+  int32_t src_stride, cin, ksize;
+  int32_t n, h, w;
+  const void* weight;
+  int64_t weight_elems;
+  const float* bias;
+  int32_t cout, relu_in, relu;
+  const void* res0;
+  const void* res1;
+  int32_t res0_stride, res1_stride;
+  void* out;
+  int32_t out_kind, out_stride;
+} SgrDptConv;
+typedef struct SgrDptWeights {
+  int32_t dim, features, chs0, chs1;
+  SgrUpdateLayer layer[SGR_DPT_LAYERS];
+} SgrDptWeights;
+typedef struct SgrDptCall {
+  SgrUpdateTensor tap3, tap4;      /* [n,dim,H/16,W/16] */
+  const void* l1;
+  const void* l2;
+  int32_t n, H, W;
+  float* depth;                    /* [n][H][W] */
+  int32_t first_launch, last_launch;
+} SgrDptCall;
+size_t sgr_dpt_scratch_bytes(int32_t n, int32_t H, int32_t W, int32_t dim, int32_t features);
+int sgr_dpt_conv(const SgrDptConv* conv, void* stream);
+int sgr_dpt_up2(const void* src, int32_t n, int32_t h, int32_t w, int32_t channels, int32_t src_stride, void* dst, int32_t dst_stride,
+                void* stream);
+int sgr_dpt_resize_in(const float* src, int32_t planes, int32_t H, int32_t W, void* dst, int32_t h, int32_t w, void* stream);
+int sgr_dpt_resize_out(const float* src, int32_t planes, int32_t h, int32_t w, float* dst, int32_t H, int32_t W, void* stream);
+int sgr_dpt_forward(const SgrDptWeights* weights, const SgrDptCall* call, void* scratch, size_t scratch_bytes, void* stream);
+
 /* SE3 ops, batched over n. Pose =(tx,ty,tz,qx,qy,qz,qw) as in lietorch / depth_video.py:69; tau = (rho, theta). */
 int se3_exp(const float* tau, int64_t n, float* pose_out, void* stream);
 int se3_log(const float* pose, int64_t n, float* tau_out, void* stream);

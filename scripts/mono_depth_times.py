@@ -6,9 +6,13 @@ two sides alternating in this one process on the same card.  A single launch is 
 Then MonoDepth's two backbones, "torch" (the default) and "hip" (splat_slam_amd.resnetv2, csrc/sgr_resnet.hip): the backbone alone and a
 whole predict, the two variants alternating, with the spread of the repeats, the difference of the two predict outputs, and the HIP
 backbone launch by launch with the bytes and operations its shapes imply.
+Then MonoDepth's two decoders, "torch" (the default) and "hip" (splat_slam_amd.dpt_decoder, csrc/sgr_dpt.hip), both on backbone="hip": a
+whole predict, the decoder alone on the same taps and stage maps, and each resize of predict, the two variants alternating with the same
+spread rule; then the 35 launches of the HIP decoder one by one with bytes, operations and workgroups from the shapes (key
+decoder_torch_vs_hip; --only decoder measures this leg alone and keeps the other keys of the output file as they are).
 Writes one JSON file (rewritten after every section, so a run that is cut short leaves what it measured).
 
-    timeout 900 python scripts/mono_depth_times.py [--out profiles/mono_depth_times.json] [--reps 10]"""
+    timeout 900 python scripts/mono_depth_times.py [--out profiles/mono_depth_times.json] [--reps 10] [--only decoder]"""
 import argparse
 import datetime
 import json
@@ -102,6 +106,116 @@ def backbone_launch_model(cfg, B, H, W):
     return out
 
 
+def decoder_launch_model(cfg, B, H, W):
+    """launch name -> (bytes, GFLOP, workgroups) of sgr_dpt_forward from the shapes alone: every map read once and written once (taps
+    re-read through the caches are not counted), residuals read once, the packed weights once"""
+    from splat_slam_amd import dpt_decoder as DD
+    D, f, out = cfg.dim, cfg.features, {}
+    gh, gw = H // 16, W // 16
+
+    def conv(name, cin, cout, k, h, w, nres=0, stride=1, out_bytes=2):
+        ho, wo = h // stride, w // stride
+        k_pad = -(-k * k * cin // 32) * 32
+        bn = 64 if cout % 64 == 0 else 32 if cout % 32 == 0 else 16
+        tiles = B * -(-ho * wo // 128) if stride == 2 else -(-B * ho * wo // 128)
+        out[name] = (B * h * w * cin * 2 + -(-cout // 64) * 64 * k_pad * 2 + B * ho * wo * cout * (out_bytes + 2 * nres),
+                     2.0 * B * ho * wo * cout * k * k * cin / 1e9, tiles * -(-cout // bn))
+
+    def up2(name, h, w, C):
+        out[name] = (B * h * w * C * 2 * 5, 0.0, -(-B * h * w * 4 * (C // 8) // 256))
+
+    out["pack3"] = (B * gh * gw * D * 4, 0.0, 0)
+    conv("act_postprocess3.3", D, D, 1, gh, gw)
+    out["pack4"] = (B * gh * gw * D * 4, 0.0, 0)
+    conv("act_postprocess4.3", D, D, 1, gh, gw)
+    conv("act_postprocess4.4", D, D, 3, gh, gw, stride=2)
+    for i, cin in enumerate((cfg.stage_chs[0], cfg.stage_chs[1], D, D)):
+        conv(f"layer{i + 1}_rn", cin, f, 3, H >> (2 + i), W >> (2 + i))
+    for i in (4, 3, 2, 1):
+        h, w, p = H >> (1 + i), W >> (1 + i), f"refinenet{i}."
+        if i < 4:
+            conv(p + "resConfUnit1.conv1", f, f, 3, h, w)
+            conv(p + "resConfUnit1.conv2", f, f, 3, h, w, 2)
+        conv(p + "resConfUnit2.conv1", f, f, 3, h, w)
+        conv(p + "resConfUnit2.conv2", f, f, 3, h, w, 1)
+        up2(p + "up2", h, w, f)
+        conv(p + "out_conv", f, f, 1, 2 * h, 2 * w)
+    conv("output_conv.0", f, f // 2, 3, H // 2, W // 2)
+    up2("head.up2", H // 2, W // 2, f // 2)
+    conv("output_conv.2", f // 2, 32, 3, H, W)
+    conv("output_conv.4", 32, 1, 1, H, W, out_bytes=4)
+    assert tuple(out) == DD.LAUNCH_NAMES(cfg)
+    return out
+
+
+def torch_decoder(m, tap3, tap4, l1, l2, B, H, W):
+    """the decoder of MonoDepth.forward with decoder="torch", backbone="hip", on given taps and stage maps: the same calls in the same
+    order"""
+    from splat_slam_amd.mono_depth import _up2
+    c = m._c
+    r4 = m._down(c["pretrained.act_postprocess4.3"](tap4))
+    skip2 = c["scratch.layer2_rn"].packed(l2, B, H // 8, W // 8)
+    skip1 = c["scratch.layer1_rn"].packed(l1, B, H // 4, W // 4)
+    r3 = c["pretrained.act_postprocess3.3"](tap3)
+    path = m._fusion(4, c["scratch.layer4_rn"](r4))
+    path = m._fusion(3, path, c["scratch.layer3_rn"](r3))
+    path = m._fusion(2, path, skip2)
+    path = m._fusion(1, path, skip1)
+    y = c["scratch.output_conv.2"](_up2(c["scratch.output_conv.0"](path)), "relu")
+    return c["scratch.output_conv.4"](y, "relu", torch.float32)[:, 0]
+
+
+def decoder_leg(res, save, reps):
+    """decoder="torch" against decoder="hip", both on backbone="hip": whole predict and the decoder alone, alternating; then the 35
+    launches and the two resizes one by one on the buffers of a whole call"""
+    import torch.nn.functional as F
+    from splat_slam_amd import dpt_decoder as DD
+    from splat_slam_amd import mono_depth as MD
+    mcfg = MD.MonoDepthConfig()
+    sd = MD.synthetic_state_dict(SEED, mcfg)
+    ref = MD.MonoDepth.from_state_dict(sd, mcfg, DEV, backbone="hip", decoder="torch")
+    hip = MD.MonoDepth.from_state_dict(sd, mcfg, DEV, backbone="hip", decoder="hip")
+    del sd
+    image = torch.rand(1, 3, 480, 640, generator=torch.Generator().manual_seed(2)).to(DEV)
+    H, W = mcfg.net_size
+    d = {"net_size": [H, W], "image": [480, 640], "backbone": "hip"}
+    d["predict"] = two_variants(lambda: ref.predict(image), lambda: hip.predict(image), reps)
+    d["max_abs_difference_of_the_two_predicts"] = float((ref.predict(image) - hip.predict(image)).abs().max())
+    x = DD.resize_in(image, (H, W))
+    l1, l2, l3 = hip.backbone.channels_last(x)
+    tap3, tap4 = hip.vit.tokens(l3, H // 16, W // 16)
+    d["decoder"] = two_variants(lambda: torch_decoder(ref, tap3, tap4, l1, l2, 1, H, W), lambda: hip.dpt(tap3, tap4, l1, l2, H, W), reps)
+    d["max_abs_difference_of_the_two_decoders"] = float((torch_decoder(ref, tap3, tap4, l1, l2, 1, H, W) - hip.dpt(tap3, tap4, l1, l2, H, W)).abs().max())
+    depth = hip.dpt(tap3, tap4, l1, l2, H, W)[0]
+    torch_in = lambda: ((F.interpolate(image, size=(H, W), mode="bilinear", align_corners=False, antialias=True) - 0.5) / 0.5).to(torch.float16)
+    torch_out = lambda: F.interpolate(depth.clamp(0, 1)[None, None], size=(480, 640), mode="bicubic").clamp(0, 1)[0, 0]
+    d["resize_in"] = two_variants(torch_in, lambda: DD.resize_in(image, (H, W)), reps)
+    d["resize_out"] = two_variants(torch_out, lambda: DD.resize_out(depth, (480, 640)), reps)
+    res["decoder_torch_vs_hip"] = d
+    save()
+    print("predict torch", d["predict"]["torch"]["ms_median"], "hip", d["predict"]["hip"]["ms_median"], "spread", d["predict"]["spread_ms"],
+          "; decoder torch", d["decoder"]["torch"]["ms_median"], "hip", d["decoder"]["hip"]["ms_median"], "spread", d["decoder"]["spread_ms"], flush=True)
+    call, _ = hip.dpt._prepare(tap3, tap4, l1, l2, H, W)
+    hip.dpt._run(call)
+    model_of = decoder_launch_model(mcfg, 1, H, W)
+    launches = {}
+    for i, name in enumerate(DD.LAUNCH_NAMES(mcfg)):
+        call.first_launch = call.last_launch = i
+        hip.dpt._run(call)
+        t = summary([one_time(lambda: hip.dpt._run(call)) for _ in range(reps)])
+        nbytes, gflop, groups = model_of[name]
+        t_bytes, t_flop = nbytes / (PEAK_HBM_TBS * 1e12) * 1e3, gflop / PEAK_F16_TFLOPS
+        t.update({"mbytes": round(nbytes / 1e6, 3), "gflop": round(gflop, 4), "workgroups": groups, "bound": "bytes" if t_bytes >= t_flop else "mfma",
+                  "ms_at_the_bound": round(max(t_bytes, t_flop), 5), "share_of_the_bound": round(max(t_bytes, t_flop) / t["ms_median"], 4)})
+        launches[name] = t
+    d["hip_launches"] = launches
+    d["hip_sum_of_launches_ms"] = round(sum(t["ms_median"] for t in launches.values()), 4)
+    d["hip_gflop"], d["hip_mbytes"] = round(sum(v[1] for v in model_of.values()), 2), round(sum(v[0] for v in model_of.values()) / 1e6, 1)
+    d["peak_hbm_tbs"] = PEAK_HBM_TBS
+    save()
+    print("decoder launches", {k: v["ms_median"] for k, v in launches.items()}, flush=True)
+
+
 def hold_fp16(params):
     """the torch side keeps its matrices and kernels in fp16, so that autocast casts no weight inside the timed call"""
     for k, v in params.items():
@@ -131,6 +245,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mono_depth_times.json"))
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--only", choices=("all", "decoder"), default="all",
+                    help="decoder: keep what the output file holds and (re)write its key decoder_torch_vs_hip alone")
     a = ap.parse_args()
     res = {"device": torch.cuda.get_device_name(0), "date": datetime.date.today().isoformat(), "peak_f16_tflops": PEAK_F16_TFLOPS}
 
@@ -138,6 +254,15 @@ def main():
         os.makedirs(os.path.dirname(a.out), exist_ok=True)
         with open(a.out, "w") as fh:
             json.dump(res, fh, indent=1)
+
+    if a.only == "decoder":
+        if os.path.exists(a.out):
+            with open(a.out) as fh:
+                res = json.load(fh)
+        decoder_leg(res, save, a.reps)
+        res["decoder_torch_vs_hip"]["device"], res["decoder_torch_vs_hip"]["date"] = torch.cuda.get_device_name(0), datetime.date.today().isoformat()
+        save()
+        return
 
     # ---- the whole transformer ----
     cfg = V.VitConfig()
@@ -228,6 +353,9 @@ def main():
     b["peak_hbm_tbs"] = PEAK_HBM_TBS
     save()
     print("backbone by kind", by_kind, flush=True)
+    del model, torch_model, hip_model, net, call, outs
+    torch.cuda.empty_cache()
+    decoder_leg(res, save, a.reps)
     print(json.dumps({k: v.get("ratio_hip_over_torch") for k, v in res.items() if isinstance(v, dict)}))
 
 

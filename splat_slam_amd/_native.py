@@ -236,6 +236,26 @@ class SgrResnetCall(C.Structure):
                 ("last_launch", C.c_int32)]
 
 
+SGR_DPT_LAYERS, SGR_DPT_LAUNCHES = 28, 35
+
+
+class SgrDptConv(C.Structure):
+    _fields_ = [("src", _fp), ("src_stride", C.c_int32), ("cin", C.c_int32), ("ksize", C.c_int32), ("n", C.c_int32), ("h", C.c_int32),
+                ("w", C.c_int32), ("weight", _fp), ("weight_elems", C.c_int64), ("bias", _fp), ("cout", C.c_int32), ("relu_in", C.c_int32),
+                ("relu", C.c_int32), ("res0", _fp), ("res1", _fp), ("res0_stride", C.c_int32), ("res1_stride", C.c_int32), ("out", _fp),
+                ("out_kind", C.c_int32), ("out_stride", C.c_int32)]
+
+
+class SgrDptWeights(C.Structure):
+    _fields_ = [("dim", C.c_int32), ("features", C.c_int32), ("chs0", C.c_int32), ("chs1", C.c_int32),
+                ("layer", SgrUpdateLayer * SGR_DPT_LAYERS)]
+
+
+class SgrDptCall(C.Structure):
+    _fields_ = [("tap3", SgrUpdateTensor), ("tap4", SgrUpdateTensor), ("l1", _fp), ("l2", _fp), ("n", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("depth", _fp), ("first_launch", C.c_int32), ("last_launch", C.c_int32)]
+
+
 SGR_RESNET_NORM_NONE, SGR_RESNET_NORM_GROUP = 0, 1
 SGR_RESNET_ACTS = {"none": 0, "relu": 1}
 SGR_VIT_EPI = {"store_f16": 1, "gelu_f16": 2, "residual": 3, "readout": 4, "embed": 5, "store_f32": 6}
@@ -381,6 +401,12 @@ SIGNATURES = {
     "sgr_resnet_groupnorm": (C.c_int, [C.POINTER(SgrResnetNorm), _fp]),
     "sgr_resnet_maxpool": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]),
     "sgr_resnet_forward": (C.c_int, [C.POINTER(SgrResnetWeights), C.POINTER(SgrResnetCall), _fp, C.c_size_t, _fp]),
+    "sgr_dpt_scratch_bytes": (C.c_size_t, [C.c_int32] * 5),
+    "sgr_dpt_conv": (C.c_int, [C.POINTER(SgrDptConv), _fp]),
+    "sgr_dpt_up2": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, _fp]),
+    "sgr_dpt_resize_in": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, C.c_int32, _fp]),
+    "sgr_dpt_resize_out": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, C.c_int32, _fp]),
+    "sgr_dpt_forward": (C.c_int, [C.POINTER(SgrDptWeights), C.POINTER(SgrDptCall), _fp, C.c_size_t, _fp]),
     "se3_exp": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_log": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_inv": (C.c_int, [_fp, C.c_int64, _fp, _fp]),

@@ -1,5 +1,5 @@
-// The convolution tile shared by the update operator (sgr_update.hip), the encoders (sgr_encoder.hip) and the ResNet-V2 backbone
-// (sgr_resnet.hip), the pieces of the two norms that are the same in both, and the host helpers of these files and of sgr_vit.hip.
+// The convolution tile shared by the update operator (sgr_update.hip), the encoders (sgr_encoder.hip), the ResNet-V2 backbone
+// (sgr_resnet.hip) and the DPT decoder (sgr_dpt.hip), the pieces of the two norms that are the same in both, and the host helpers of these files and of sgr_vit.hip.
 // DESIGN.md section 3, "Update operator", describes the tile.
 //
 // The GEMM is D[n][m] = sum_k W[n][k] X[m][k] with m a pixel, n an output channel and k = tap * cin + channel: the weights are the A
@@ -60,6 +60,61 @@ __device__ __forceinline__ void conv_mma_mainloop(half_t* Xs, half_t* Ws, const 
   for (int kt = 0; kt < nk; ++kt) {
     *(half8*)&Xs[srow * kRow + kc * 8] = xr[0];
     *(half8*)&Xs[(srow + 64) * kRow + kc * 8] = xr[1];
+    if (wv) *(half8*)&Ws[srow * kRow + kc * 8] = wr;
+    __syncthreads();
+    if (kt + 1 < nk) {
+      ch += kBK;
+      while (ch >= cin) {
+        ch -= cin;
+        ++tap;
+      }
+      gload(kt + 1);
+    }
+    half8 bf[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) bf[j] = *(const half8*)&Xs[(wave * 32 + j * 16 + (lane & 15)) * kRow + (lane >> 4) * 8];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const half8 af = *(const half8*)&Ws[(t * 16 + (lane & 15)) * kRow + (lane >> 4) * 8];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc[t][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[j], acc[t][j], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+}
+
+// The same k loop with a map over the gathered pixel chunks, applied where they go to LDS: pre(chunk) runs one k step after the load
+// that fetched the chunk, behind the MFMAs of the step before, so that the loads stay in flight as above (a map inside gather would
+// wait for its load at once).  Same staging, same order of every sum as conv_mma_mainloop.
+template <int KS, int BN, class Gather, class Pre>
+__device__ __forceinline__ void conv_mma_mainloop_pre(half_t* Xs, half_t* Ws, const half_t* weight, int n0, int k_pad, int cin, Gather&& gather,
+                                                      Pre&& pre, floatx4 (&acc)[BN / 16][2]) {
+  constexpr int NT = BN / 16;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int kc = tid & 3, srow = tid >> 2;
+  const bool wv = tid < BN * 4;
+  const half_t* wp = weight + (size_t)(n0 + (wv ? srow : 0)) * k_pad + kc * 8;
+
+  int tap = (kc * 8) / cin, ch = (kc * 8) % cin;
+  half8 xr[2], wr;
+  auto gload = [&](int kt) {
+    const int ty = tap / KS, tx = tap % KS;
+    const bool tv = tap < KS * KS;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) xr[i] = gather(i, tv, ty, tx, ch);
+    if (wv) wr = *(const half8*)(wp + (size_t)kt * kBK);
+  };
+
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[t][j] = floatx4{0.f, 0.f, 0.f, 0.f};
+
+  const int nk = k_pad / kBK;
+  gload(0);
+  for (int kt = 0; kt < nk; ++kt) {
+    *(half8*)&Xs[srow * kRow + kc * 8] = pre(xr[0]);
+    *(half8*)&Xs[(srow + 64) * kRow + kc * 8] = pre(xr[1]);
     if (wv) *(half8*)&Ws[srow * kRow + kc * 8] = wr;
     __syncthreads();
     if (kt + 1 < nk) {

@@ -2,8 +2,9 @@
 thirdparty/mono_priors/omnidata/modules/midas/{dpt_depth,blocks,vit}.py), inference only, usable as Slam(..., mono_depth=MonoDepth...).
 
     MonoDepthConfig()                                     the reference's network; every width is a field
-    MonoDepth.from_state_dict(sd, cfg=MonoDepthConfig(), device="cuda", backbone="torch")
-    MonoDepth.synthetic(seed, cfg=MonoDepthConfig(), device="cuda", backbone="torch")      backbone: "torch" (the default) or "hip"
+    MonoDepth.from_state_dict(sd, cfg=MonoDepthConfig(), device="cuda", backbone="torch", decoder="torch")
+    MonoDepth.synthetic(seed, cfg=MonoDepthConfig(), device="cuda", backbone="torch", decoder="torch")
+                                                          backbone, decoder: "torch" (the default) or "hip", independently
     m.forward(x [B,3,H,W]) -> [B,H,W] fp32                H and W multiples of 32; the network on a normalised image
     m.predict(image [1,3,H,W] in [0,1]) -> [H,W] fp32     the reference's predict_mono_depth without its file
     m(timestamp, image)                                   predict(image): the callable Slam, Tracker and MotionFilter take
@@ -19,8 +20,12 @@ once.  With backbone="torch" the ResNet-V2 backbone, the one 3x3 stride-2 reasse
 fp16 with fp32 group norms; those convolutions run the vendor library's deterministic algorithm, so forward and predict repeat bit
 for bit.  With backbone="hip" self.backbone is a splat_slam_amd.resnetv2.ResNetV2 on the sgr_resnet_* kernels: its stage maps stay
 channels-last (the transformer and layer1_rn / layer2_rn read them without a copy or a pack launch), the stride-2 reassemble
-convolution runs on sgr_resnet_conv, and an image inside a batch gives the bits of the image alone.  Adds, ReLU and all resampling of
-the decoder and the two resizes of predict are torch ops in both settings.  A CPU tensor or a missing kernel is an error: there is no
+convolution runs on sgr_resnet_conv, and an image inside a batch gives the bits of the image alone.  With decoder="torch" the adds,
+ReLU and all resampling of the decoder and the two resizes of predict are torch ops, and every decoder convolution converts NCHW to
+channels-last and back.  With decoder="hip" self.dpt is a
+splat_slam_amd.dpt_decoder.DPTDecoder on the sgr_dpt_* kernels: every map from the stage maps to the depth plane stays channels-last
+fp16, the decoder is one host call of 35 launches without a torch op in between (the adds and ReLUs sit in the convolutions' gathers
+and epilogues), and predict runs each of its two resizes as one launch.  A CPU tensor or a missing kernel is an error: there is no
 eager fallback.
 
 Both state-dict functions accept the checkpoint's {"state_dict": ...} wrapper, whose keys lose their first 6 characters as in the
@@ -264,14 +269,18 @@ def _up2(x):
 
 
 BACKBONES = ("torch", "hip")
+DECODERS = ("torch", "hip")
 
 
 class MonoDepth:
-    def __init__(self, sd, cfg=MonoDepthConfig(), device="cuda", backbone="torch"):
+    def __init__(self, sd, cfg=MonoDepthConfig(), device="cuda", backbone="torch", decoder="torch"):
         if backbone not in BACKBONES:
             raise ValueError(f"mono_depth: backbone must be one of {BACKBONES}, got {backbone!r}")
+        if decoder not in DECODERS:
+            raise ValueError(f"mono_depth: decoder must be one of {DECODERS}, got {decoder!r}")
         sd = normalize_state_dict(sd, cfg)
         self.backbone_kind = backbone
+        self.decoder_kind = decoder
         self.cfg = cfg
         self.device = dev = torch.device(device)
         if dev.type != "cuda":
@@ -301,14 +310,17 @@ class MonoDepth:
             from splat_slam_amd.resnetv2 import ResNetV2
             self.backbone = ResNetV2({k: v for k, v in sd.items() if k.startswith(_BACKBONE)}, cfg, dev)
             self._down = _DownConv(self._down_w, self._down_b, dev)
+        if decoder == "hip":
+            from splat_slam_amd.dpt_decoder import DPTDecoder
+            self.dpt = DPTDecoder(sd, cfg, dev)
 
     @classmethod
-    def from_state_dict(cls, sd, cfg=MonoDepthConfig(), device="cuda", backbone="torch"):
-        return cls(sd, cfg, device, backbone)
+    def from_state_dict(cls, sd, cfg=MonoDepthConfig(), device="cuda", backbone="torch", decoder="torch"):
+        return cls(sd, cfg, device, backbone, decoder)
 
     @classmethod
-    def synthetic(cls, seed, cfg=MonoDepthConfig(), device="cuda", backbone="torch"):
-        return cls(synthetic_state_dict(seed, cfg), cfg, device, backbone)
+    def synthetic(cls, seed, cfg=MonoDepthConfig(), device="cuda", backbone="torch", decoder="torch"):
+        return cls(synthetic_state_dict(seed, cfg), cfg, device, backbone, decoder)
 
     # ---- the torch part: ResNet-V2 stem and stages in fp16, group norms in fp32 ----
     def _norm(self, name, x, relu):
@@ -350,6 +362,8 @@ class MonoDepth:
             raise RuntimeError("mono_depth (MI355X build): x must be a GPU tensor; there is no CPU path")
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1 or x.shape[2] < 32 or x.shape[2] % 32 or x.shape[3] < 32 or x.shape[3] % 32:
             raise ValueError(f"mono_depth: x must be [B,3,H,W] with H and W positive multiples of 32, got {tuple(x.shape)}")
+        if self.decoder_kind == "hip":
+            return self._forward_hip_decoder(x)
         c = self._c
         if self.backbone_kind == "hip":
             # the stage maps stay channels-last: l3 is the transformer's patches, l1 and l2 are packed inputs of layer1_rn and layer2_rn
@@ -372,11 +386,29 @@ class MonoDepth:
         y = c["scratch.output_conv.2"](_up2(c["scratch.output_conv.0"](path)), "relu")
         return c["scratch.output_conv.4"](y, "relu", torch.float32)[:, 0]
 
+    def _forward_hip_decoder(self, x):
+        """every map channels-last fp16 from the stage maps to the depth plane: the decoder is one call of sgr_dpt_forward"""
+        from splat_slam_amd.dpt_decoder import pack_nchw
+        B, _, H, W = x.shape
+        x = x.to(self.device, torch.float16)
+        if self.backbone_kind == "hip":
+            l1, l2, l3 = self.backbone.channels_last(x)
+            tap3, tap4 = self.vit.tokens(l3, H // 16, W // 16)
+        else:
+            l1, l2, l3 = self.backbone(x)
+            tap3, tap4 = self.vit(l3)
+            l1, l2 = pack_nchw(l1), pack_nchw(l2)
+        return self.dpt(tap3, tap4, l1, l2, H, W)
+
     def predict(self, image):
         if not isinstance(image, torch.Tensor) or not image.is_cuda:
             raise RuntimeError("mono_depth (MI355X build): image must be a GPU tensor; there is no CPU path")
         if image.dim() != 4 or image.shape[0] != 1 or image.shape[1] != 3:
             raise ValueError(f"mono_depth: image must be [1,3,H,W], got {tuple(image.shape)}")
+        if self.decoder_kind == "hip":
+            from splat_slam_amd.dpt_decoder import resize_in, resize_out
+            depth = self.forward(resize_in(image.float(), tuple(self.cfg.net_size)))
+            return resize_out(depth[0], tuple(image.shape[-2:]))
         x = F.interpolate(image.float(), size=tuple(self.cfg.net_size), mode="bilinear", align_corners=False, antialias=True)
         out = self.forward((x - 0.5) / 0.5).clamp(0, 1)
         return F.interpolate(out[None], size=tuple(image.shape[-2:]), mode="bicubic").clamp(0, 1)[0, 0]
