@@ -20,6 +20,8 @@
  *                             thirdparty/monogs/utils/slam_utils.py:89-98, imported at src/mapper.py:35) and its autograd backward
  *   sgr_render_metrics     -> the PSNR / SSIM / depth-L1 part of eval_rendering, src/utils/eval_utils.py:90-128, called from
  *                             src/slam.py:153,193
+ *   sgr_lpips_*            -> the LPIPS part of the same function (eval_utils.py:66-68, 125, 192: torchmetrics'
+ *                             LearnedPerceptualImagePatchSimilarity(net_type="alex", normalize=True))
  *   sgr_tsdf_*, sgr_mesh_* -> the mesh branch of the same function (eval_utils.py:70-74, 142-179: Open3D's ScalableTSDFVolume
  *                             integrate / extract_triangle_mesh) and clean_mesh (:331-379, trimesh connected components)
  *   sgr_surface_sample*, sgr_nn_*, sgr_icp_accumulate, sgr_cloud_metrics, sgr_eval_reduce_bytes
@@ -1202,6 +1204,67 @@ int sgr_dpt_up2(const void* src, int32_t n, int32_t h, int32_t w, int32_t channe
 int sgr_dpt_resize_in(const float* src, int32_t planes, int32_t H, int32_t W, void* dst, int32_t h, int32_t w, void* stream);
 int sgr_dpt_resize_out(const float* src, int32_t planes, int32_t h, int32_t w, float* dst, int32_t H, int32_t W, void* stream);
 int sgr_dpt_forward(const SgrDptWeights* weights, const SgrDptCall* call, void* scratch, size_t scratch_bytes, void* stream);
+
+/* LPIPS v0.1 on the AlexNet trunk, the third image figure of eval_rendering (eval_utils.py:66-68, 125, 192), inference only.  Stated in
+ * DESIGN.md section 3, "LPIPS".  Everything is stream-ordered, allocates nothing, synchronises nothing, uses no atomics and is bitwise
+ * reproducible; a pair gives the same bits alone and inside any batch.  Maps are channels-last fp16 [image][y][x][channel], 16-byte
+ * aligned.  A call on n pairs works on 2n images: image i is the first and image n + i the second member of pair i.
+ * sgr_lpips_pack: frames (host table, n <= SGR_LPIPS_MAX_PAIRS; depth fields unused) -> dst [2n][H][W][8]: channels 0..2 =
+ * (2 img - 1 - shift[c]) / scale[c], channels 3..7 = 0; img = clamp(exp(a) render + b, 0, 1) for image i (NULL exposure = identity),
+ * the ground truth for image n + i.  sgr_lpips_pack_pairs: the same from img0, img1 fp32 [n][3][H][W], taken as they are; with
+ * normalize 0 the value is (img - shift[c]) / scale[c].  shift and scale are host arrays of 3.
+ * sgr_lpips_conv: relu(conv(src) + bias), ksize 11, 5 or 3, stride 1 or 4, symmetric zero padding pad < ksize, cin a multiple of 8,
+ * cout a multiple of 64, both up to 1024: [n][h][w][cin] -> [n][ho][wo][cout], ho = (h + 2 pad - ksize) / stride + 1.  weight is fp16
+ * [cout][round_up(ksize^2 * cin, 32)], k = tap * cin + c, padding zero; bias fp32 [cout].
+ * sgr_lpips_maxpool: 3x3, stride 2, no padding: [n][h][w][channels] -> [n][(h - 3) / 2 + 1][(w - 3) / 2 + 1][channels], channels a
+ * multiple of 8, h and w >= 3.
+ * sgr_lpips_distance: maps [2n][P][C] (C one of 64, 192, 256, 384), weight fp32 [C] -> partials [n][ceil(P / SGR_LPIPS_DIST_PIXELS)],
+ * the sums over a workgroup's pixels p of d_p = sum_c w_c (u_c - v_c)^2, u = f0 / sqrt(1e-8 + sum f0^2), v likewise; per_pixel (or
+ * NULL) [n][P] receives every d_p.  u and v are rounded to fp32 before they are subtracted, so equal maps give exactly 0 and
+ * swapped maps the same bits.
+ * sgr_lpips_forward: the SGR_LPIPS_LAUNCHES launches pack, conv1, distance1, pool1, conv2, distance2, pool2, conv3, distance3, conv4,
+ * distance4, conv5, distance5, final; first_launch <= i <= last_launch are enqueued.  The input is the frame table when frames is
+ * set, otherwise img0 / img1.  out [n] = the sum of the five tap means (each merged in fp64 in a fixed order); levels (or NULL)
+ * [n][5] the tap means.  1 <= n <= SGR_LPIPS_MAX_PAIRS, H and W >= 31.  scratch: sgr_lpips_scratch_bytes(n, H, W) bytes, 16-byte
+ * aligned (0 = unsupported sizes). */
+#define SGR_LPIPS_MAX_PAIRS 16
+#define SGR_LPIPS_DIST_PIXELS 128
+#define SGR_LPIPS_LAUNCHES 14
+typedef struct SgrLpipsConv {
+  const void* src;
+  int32_t n, h, w, cin;
+  int32_t ksize, stride, pad;
+  const void* weight;
+  int64_t weight_elems;
+  const float* bias;
+  int32_t cout;
+  void* out;
+} SgrLpipsConv;
+typedef struct SgrLpipsWeights {
+  SgrUpdateLayer conv[5];          /* packed as for sgr_lpips_conv: 3(8)->64 11x11, 64->192 5x5, 192->384, 384->256, 256->256 3x3 */
+  const float* lin[5];             /* fp32 [64], [192], [384], [256], [256] */
+  float shift[3], scale[3];
+} SgrLpipsWeights;
+typedef struct SgrLpipsCall {
+  const SgrMetricFrame* frames;    /* host array [n], or NULL */
+  const float* img0;               /* [n][3][H][W], read when frames is NULL */
+  const float* img1;
+  int32_t normalize;               /* of img0 / img1: 2 x - 1 first */
+  int32_t n, H, W;
+  float* out;                      /* [n] */
+  float* levels;                   /* [n][5], or NULL */
+  int32_t first_launch, last_launch;
+} SgrLpipsCall;
+size_t sgr_lpips_scratch_bytes(int32_t n, int32_t H, int32_t W);
+int sgr_lpips_pack(int32_t n, const SgrMetricFrame* frames, int32_t H, int32_t W, const float* shift, const float* scale, void* dst,
+                   void* stream);
+int sgr_lpips_pack_pairs(const float* img0, const float* img1, int32_t n, int32_t H, int32_t W, int32_t normalize, const float* shift,
+                         const float* scale, void* dst, void* stream);
+int sgr_lpips_conv(const SgrLpipsConv* conv, void* stream);
+int sgr_lpips_maxpool(const void* src, int32_t n, int32_t h, int32_t w, int32_t channels, void* dst, void* stream);
+int sgr_lpips_distance(const void* maps, int32_t n, int32_t P, int32_t C, const float* weight, float* partials, float* per_pixel,
+                       void* stream);
+int sgr_lpips_forward(const SgrLpipsWeights* weights, const SgrLpipsCall* call, void* scratch, size_t scratch_bytes, void* stream);
 
 /* SE3 ops, batched over n. Pose =(tx,ty,tz,qx,qy,qz,qw) as in lietorch / depth_video.py:69; tau = (rho, theta). */
 int se3_exp(const float* tau, int64_t n, float* pose_out, void* stream);

@@ -256,6 +256,24 @@ class SgrDptCall(C.Structure):
                 ("W", C.c_int32), ("depth", _fp), ("first_launch", C.c_int32), ("last_launch", C.c_int32)]
 
 
+SGR_LPIPS_MAX_PAIRS, SGR_LPIPS_DIST_PIXELS, SGR_LPIPS_LAUNCHES = 16, 128, 14
+
+
+class SgrLpipsConv(C.Structure):
+    _fields_ = [("src", _fp), ("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("cin", C.c_int32), ("ksize", C.c_int32),
+                ("stride", C.c_int32), ("pad", C.c_int32), ("weight", _fp), ("weight_elems", C.c_int64), ("bias", _fp), ("cout", C.c_int32),
+                ("out", _fp)]
+
+
+class SgrLpipsWeights(C.Structure):
+    _fields_ = [("conv", SgrUpdateLayer * 5), ("lin", _fp * 5), ("shift", C.c_float * 3), ("scale", C.c_float * 3)]
+
+
+class SgrLpipsCall(C.Structure):
+    _fields_ = [("frames", C.POINTER(SgrMetricFrame)), ("img0", _fp), ("img1", _fp), ("normalize", C.c_int32), ("n", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("out", _fp), ("levels", _fp), ("first_launch", C.c_int32), ("last_launch", C.c_int32)]
+
+
 SGR_RESNET_NORM_NONE, SGR_RESNET_NORM_GROUP = 0, 1
 SGR_RESNET_ACTS = {"none": 0, "relu": 1}
 SGR_VIT_EPI = {"store_f16": 1, "gelu_f16": 2, "residual": 3, "readout": 4, "embed": 5, "store_f32": 6}
@@ -407,6 +425,15 @@ SIGNATURES = {
     "sgr_dpt_resize_in": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, C.c_int32, _fp]),
     "sgr_dpt_resize_out": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, C.c_int32, C.c_int32, _fp]),
     "sgr_dpt_forward": (C.c_int, [C.POINTER(SgrDptWeights), C.POINTER(SgrDptCall), _fp, C.c_size_t, _fp]),
+    "sgr_lpips_scratch_bytes": (C.c_size_t, [C.c_int32] * 3),
+    "sgr_lpips_pack": (C.c_int, [C.c_int32, C.POINTER(SgrMetricFrame), C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                 _fp, _fp]),
+    "sgr_lpips_pack_pairs": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                       _fp, _fp]),
+    "sgr_lpips_conv": (C.c_int, [C.POINTER(SgrLpipsConv), _fp]),
+    "sgr_lpips_maxpool": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]),
+    "sgr_lpips_distance": (C.c_int, [_fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp]),
+    "sgr_lpips_forward": (C.c_int, [C.POINTER(SgrLpipsWeights), C.POINTER(SgrLpipsCall), _fp, C.c_size_t, _fp]),
     "se3_exp": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_log": (C.c_int, [_fp, C.c_int64, _fp, _fp]),
     "se3_inv": (C.c_int, [_fp, C.c_int64, _fp, _fp]),

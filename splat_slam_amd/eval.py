@@ -5,7 +5,8 @@ loss_utils.ssim, thirdparty/gaussian_splatting/utils/loss_utils.py:61-101) and t
 torch formulation.  With mesh=True, eval_rendering also fuses every frame into a TSDF volume and returns the cleaned
 mesh (:70-74, 142-179, clean_mesh :331-379) from the HIP kernels of splat_slam_amd.mesh; given a ground-truth mesh it also
 scores that mesh (:174-187: accuracy, completion, completion ratio, precision, F-score and chamfer-L1 after ICP alignment) on the
-HIP kernels of splat_slam_amd.mesh_eval.  LPIPS is not computed: it needs pretrained AlexNet weights from outside the project."""
+HIP kernels of splat_slam_amd.mesh_eval.  Given an `splat_slam_amd.lpips.LPIPS` object, eval_rendering also reports LPIPS (:66-68, 125,
+192) from the HIP kernels of splat_slam_amd.lpips; the project ships no trained AlexNet weights, the object loads the caller's."""
 import numpy as np
 import torch
 
@@ -45,13 +46,17 @@ def _device_depth(d, device):
 @torch.no_grad()
 def eval_rendering(frames, gaussians, pipe, background, gt_depths=None, global_scale=1.0, mesh=False, mesh_path=None, c2w=None,
                    voxel_length=5.0 / 512.0, sdf_trunc=0.04, eval_mesh=True, gt_mesh_path=None, distance_thresh=0.05, icp_align=True,
-                   mesh_samples=200_000):
+                   mesh_samples=200_000, lpips=None):
     """eval_rendering's per-frame metrics (eval_utils.py:90-128, means as :190-194) on the HIP kernels: frames is a list of Camera
     in keyframe order; every frame but the first gets its exposure compensation (:96-99), the image is clamped to [0, 1];
     PSNR over the elements where the ground truth is > 0 (:109,123), SSIM of the whole image (:124), depth L1 of
     global_scale * rendered depth over pixels where both depths are > 0 (:116-120).  gt_depths: one [H,W] per frame (default:
     each frame's `depth`).  One copy to the host per call.  A frame without a valid depth pixel gives NaN (the reference's 0/0), a
-    perfect frame PSNR inf.  LPIPS is not computed (module docstring).
+    perfect frame PSNR inf.
+    lpips: an splat_slam_amd.lpips.LPIPS object (:66-68, 125): the result gains "lpips", LPIPS(image, ground truth) per frame on the
+    same clamped, exposure-compensated image, and "mean_lpips" (:192); each chunk of 16 frames is measured from the table of
+    sgr_render_metrics while its renders are alive, and the values come back in one more copy to the host.  Frames must be 3 x H x W
+    with H and W at least 31 (ValueError before anything is rendered).  With None the result is what it is without the argument.
     mesh=True (:70-74, 142-179): each frame's render of the metrics chunk is also fused into a TSDF volume (voxel_length, sdf_trunc,
     depth_trunc 30) with the exposure-compensated colour and global_scale * rendered depth, dropped where the ground-truth depth is
     0, at the pose c2w[k] (camera -> world 4x4, the reference's traj_est_aligned; default each frame's own pose).  The result gains
@@ -72,6 +77,15 @@ def eval_rendering(frames, gaussians, pipe, background, gt_depths=None, global_s
         raise RuntimeError("eval_rendering needs GPU tensors (HIP only, no CPU fallback)")
     C, H, W = frames[0].original_image.shape
     n = len(frames)
+    lp_out = None
+    if lpips is not None:
+        from splat_slam_amd.lpips import tap_sizes
+        if C != 3:
+            raise ValueError(f"eval_rendering(lpips=...): colour frames must have 3 channels, not {C}")
+        tap_sizes(H, W)
+        if lpips.device != (dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())):
+            raise RuntimeError(f"eval_rendering(lpips=...): the frames are on {dev}, the metric on {lpips.device}")
+        lp_out = torch.empty(n, dtype=torch.float32, device=dev)
     scratch_bytes = lib.sgr_ssim_scratch_bytes(_METRIC_CHUNK, C, H, W)
     arena = torch.empty(3 * n + scratch_bytes // 4, dtype=torch.float32, device=dev)
     out, scratch = arena[:3 * n], arena[3 * n:]
@@ -104,6 +118,8 @@ def eval_rendering(frames, gaussians, pipe, background, gt_depths=None, global_s
                                            (nat.C.c_float * 16)(*[float(x) for x in pose.reshape(-1)]), float(global_scale))
         nat.check(lib.sgr_render_metrics(len(table), table, C, H, W, float(global_scale), out[3 * c0:].data_ptr(), scratch.data_ptr(),
                                          scratch_bytes, stream), "sgr_render_metrics")
+        if lpips is not None:
+            lpips.frames(table, H, W, lp_out[c0:])
         if mesh:
             if C != 3:
                 raise ValueError(f"eval_rendering(mesh=True): colour frames must have 3 channels, not {C}")
@@ -112,6 +128,9 @@ def eval_rendering(frames, gaussians, pipe, background, gt_depths=None, global_s
     psnr_l, ssim_l, depth_l = (vals[:, j].tolist() for j in range(3))
     result = {"psnr": psnr_l, "ssim": ssim_l, "depth_l1": depth_l, "mean_psnr": float(np.mean(psnr_l)),
               "mean_ssim": float(np.mean(ssim_l)), "mean_depthl1": float(np.mean(depth_l))}
+    if lpips is not None:
+        result["lpips"] = lp_out.cpu().double().tolist()            # one more copy to the host
+        result["mean_lpips"] = float(np.mean(result["lpips"]))
     if mesh:
         from splat_slam_amd.mesh import clean_mesh
         result["mesh"] = clean_mesh(volume.extract_triangle_mesh(), min_len=100)

@@ -196,9 +196,10 @@ class MappingSession:
         return eval_rendering_psnr(frames, self.loop.gaussians, PipelineParams(), self.loop.background)
 
     def evaluate(self, gt_depths=None, global_scale=1.0, mesh=False, mesh_path=None, gt_mesh_path=None, distance_thresh=0.05,
-                 icp_align=True, mesh_samples=200_000):
+                 icp_align=True, mesh_samples=200_000, lpips=None):
         """eval_rendering (eval_utils.py:64-197, called at slam.py:153,193) over the session's keyframes in keyframe order: per-frame
-        and mean PSNR, SSIM and depth L1 (splat_slam_amd.eval.eval_rendering); with mesh=True also the cleaned TSDF mesh under
+        and mean PSNR, SSIM and depth L1 (splat_slam_amd.eval.eval_rendering), with an splat_slam_amd.lpips.LPIPS object as `lpips`
+        also "lpips" and "mean_lpips"; with mesh=True also the cleaned TSDF mesh under
         "mesh", written as PLY to mesh_path when given, and with a ground-truth mesh gt_mesh_path (PLY path or TriangleMesh) its
         accuracy and completion metrics under "mesh_metrics" (:174-187)."""
         from splat_slam_amd.eval import eval_rendering
@@ -206,4 +207,4 @@ class MappingSession:
         frames = [self.loop.viewpoints[k] for k in sorted(self.loop.viewpoints)]
         return eval_rendering(frames, self.loop.gaussians, PipelineParams(), self.loop.background, gt_depths=gt_depths,
                               global_scale=global_scale, mesh=mesh, mesh_path=mesh_path, gt_mesh_path=gt_mesh_path,
-                              distance_thresh=distance_thresh, icp_align=icp_align, mesh_samples=mesh_samples)
+                              distance_thresh=distance_thresh, icp_align=icp_align, mesh_samples=mesh_samples, lpips=lpips)
