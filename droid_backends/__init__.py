@@ -23,6 +23,14 @@ The correlation lookups of the update operator (modules/droid_net/corr.py), back
         levels: 1 to 4 maps [F, H >> l, W >> l, C], all fp16 or all fp32; src, dst int64 frame indices.  One launch: level l fills the
         channels [l*rd*rd, (l+1)*rd*rd) with altcorr_forward(levels[0][src], levels[l][dst], coords / 2^l).  A level without pixels
         and an edge with an index outside [0, F) give zeros; an edge gives the same bits alone and inside any batch; radius <= 4.
+    corr_volume_pyramid(maps [planes,C,h,w] fp16, src [E], dst [E], levels, slots [E]) -> None                          (in place)
+        levels: 1 to 4 stores [capacity, h, w, h >> l, w >> l] fp16; src, dst int64 plane indices, slots int64.  One launch writes,
+        into slot slots[e] of every level, the all-pairs correlation of planes src[e] and dst[e] divided by 16 (MFMA, fp32 sums) and
+        its 2^l x 2^l block means, each level rounded to fp16 once (include/splat_hip.h states the order).  An edge with a plane
+        outside [0, planes) zeroes its slot, a slot outside [0, capacity) is skipped; C is a multiple of 32 up to 1024, E <= 65535.
+    corr_index_pyramid_forward(levels, slots [E], coords [E,h,w,2] fp32, radius) -> [corr [E,len(levels)*rd*rd,h,w]]    (fp16)
+        one launch: the channels [l*rd*rd, (l+1)*rd*rd) are bit for bit corr_index_forward(levels[l][slots], coords / 2^l, radius).
+        A level without pixels and a slot outside [0, capacity) give zeros; radius <= 4.
 
 Outputs run over the x offset first, then the y offset, as in the reference.  A sample is bilinear with zero padding, summed in fp32
 and rounded once.  A pixel whose floor(x0) or floor(y0) is not finite, or lies more than radius+2 outside the map, gives exact zeros
@@ -38,7 +46,7 @@ import torch
 from splat_slam_amd import _native as nat
 
 __all__ = ["ba", "frame_distance", "projmap", "depth_filter", "iproj", "corr_index_forward", "corr_index_backward", "altcorr_forward",
-           "altcorr_backward", "altcorr_pyramid_forward"]
+           "altcorr_backward", "altcorr_pyramid_forward", "corr_volume_pyramid", "corr_index_pyramid_forward"]
 
 
 def _gpu(name, t, dtype, ndim=None):
@@ -350,4 +358,74 @@ def altcorr_pyramid_forward(levels, src, dst, coords, radius):
         nat.check(nat.lib().sgr_corr_alt_pyramid_forward(*ptrs, src.data_ptr(), dst.data_ptr(), coords.data_ptr(), corr.data_ptr(),
                                                          nat.SGR_CORR_F16 if dtype == torch.float16 else nat.SGR_CORR_F32, F, E, H, W, C,
                                                          radius, len(levels), _stream(dev)), "sgr_corr_alt_pyramid_forward")
+    return [corr]
+
+
+def _volume_levels(fn, levels):
+    """the stores of a volume pyramid: 1 to 4 contiguous fp16 tensors [capacity, h, w, h >> l, w >> l]; returns (capacity, h, w)"""
+    if not isinstance(levels, (list, tuple)) or not 1 <= len(levels) <= nat.SGR_CORR_PYRAMID_MAX_LEVELS:
+        raise ValueError(f"droid_backends.{fn}: levels must be a list of 1 to {nat.SGR_CORR_PYRAMID_MAX_LEVELS} tensors")
+    for l, v in enumerate(levels):
+        _gpu(f"levels[{l}]", v, torch.float16, 5)
+    cap, h, w = levels[0].shape[:3]
+    for l, v in enumerate(levels):
+        if tuple(v.shape) != (cap, h, w, h >> l, w >> l):
+            raise ValueError(f"droid_backends.{fn}: levels[{l}] must be [capacity, h, w, h >> {l}, w >> {l}] = "
+                             f"{(cap, h, w, h >> l, w >> l)}, got {tuple(v.shape)}")
+    if cap < 1 or h < 1 or w < 1:
+        raise ValueError(f"droid_backends.{fn}: levels[0] must be [capacity,h,w,h,w] with capacity, h, w > 0, got {tuple(levels[0].shape)}")
+    if cap > _I32 or h * w > _I32 - 512:
+        raise ValueError(f"droid_backends.{fn}: capacity and h*w must each fit in int32")
+    return cap, h, w
+
+
+def _level_ptrs(levels):
+    return [v.data_ptr() if v.numel() else None for v in levels] + [None] * (nat.SGR_CORR_PYRAMID_MAX_LEVELS - len(levels))
+
+
+def corr_volume_pyramid(maps, src, dst, levels, slots):
+    fn = "corr_volume_pyramid"
+    _gpu("maps", maps, torch.float16, 4)
+    cap, h, w = _volume_levels(fn, levels)
+    planes, C = maps.shape[:2]
+    if tuple(maps.shape) != (planes, C, h, w) or planes < 1:
+        raise ValueError(f"droid_backends.{fn}: maps must be [planes,C,h,w] with planes > 0 and h, w = {(h, w)}, got {tuple(maps.shape)}")
+    E = _edges(src, dst)
+    _gpu("slots", slots, torch.int64, 1)
+    if slots.shape[0] != E:
+        raise ValueError(f"droid_backends.{fn}: slots must have one entry per edge ({E}), got {slots.shape[0]}")
+    if C < nat.SGR_CORR_VOLUME_CHANNEL_STEP or C % nat.SGR_CORR_VOLUME_CHANNEL_STEP or C > nat.SGR_CORR_VOLUME_MAX_CHANNELS:
+        raise ValueError(f"droid_backends.{fn}: the channel count must be a positive multiple of {nat.SGR_CORR_VOLUME_CHANNEL_STEP} up to "
+                         f"{nat.SGR_CORR_VOLUME_MAX_CHANNELS}, got {C}")
+    if planes > _I32 or E > nat.SGR_CORR_VOLUME_MAX_EDGES:
+        raise ValueError(f"droid_backends.{fn}: planes must fit in int32 and there may be at most {nat.SGR_CORR_VOLUME_MAX_EDGES} edges")
+    dev = _same_device(maps, *levels, src, dst, slots)
+    if E == 0:
+        return
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().sgr_corr_volume_pyramid(maps.data_ptr(), src.data_ptr(), dst.data_ptr(), slots.data_ptr(), *_level_ptrs(levels),
+                                                    planes, E, cap, C, h, w, len(levels), _stream(dev)), "sgr_corr_volume_pyramid")
+
+
+def corr_index_pyramid_forward(levels, slots, coords, radius):
+    fn = "corr_index_pyramid_forward"
+    cap, h, w = _volume_levels(fn, levels)
+    _gpu("slots", slots, torch.int64, 1)
+    _gpu("coords", coords, torch.float32, 4)
+    E = slots.shape[0]
+    if tuple(coords.shape) != (E, h, w, 2):
+        raise ValueError(f"droid_backends.{fn}: coords must be [E,h,w,2] = {(E, h, w, 2)}, got {tuple(coords.shape)}")
+    radius = _radius(fn, radius)
+    if radius > nat.SGR_CORR_PYRAMID_MAX_RADIUS:
+        raise ValueError(f"droid_backends.{fn}: radius {radius} exceeds the supported {nat.SGR_CORR_PYRAMID_MAX_RADIUS}")
+    if E * h * w > _I32:
+        raise ValueError(f"droid_backends.{fn}: E*h*w must fit in int32")
+    dev = _same_device(*levels, slots, coords)
+    rd = 2 * radius + 1
+    corr = torch.empty((E, len(levels) * rd * rd, h, w), dtype=torch.float16, device=dev)
+    if E == 0:
+        return [corr]
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().sgr_corr_index_pyramid_forward(*_level_ptrs(levels), slots.data_ptr(), coords.data_ptr(), corr.data_ptr(), cap, E,
+                                                           h, w, radius, len(levels), _stream(dev)), "sgr_corr_index_pyramid_forward")
     return [corr]

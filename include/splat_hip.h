@@ -808,6 +808,29 @@ int sgr_corr_alt_backward(const float* fmap1, const float* fmap2, const float* c
 int sgr_corr_alt_pyramid_forward(const void* level0, const void* level1, const void* level2, const void* level3, const int64_t* src,
                                  const int64_t* dst, const float* coords, float* corr, int32_t dtype, int32_t frames, int32_t edges,
                                  int32_t h, int32_t w, int32_t channels, int32_t radius, int32_t num_levels, void* stream);
+/* The all-pairs correlation volumes of a batch of edges, written into the slots of a store, and the lookup that reads them there.
+ * Stated in DESIGN.md section 3, "Fused correlation volume".  Both calls are stream-ordered, allocate nothing, synchronise nothing,
+ * use no atomics and are bitwise reproducible; indices into the levels are 64-bit.
+ * level_l [capacity, h, w, h >> l, w >> l] fp16, l < num_levels <= 4 (the others are ignored; a level without pixels may be NULL).
+ * sgr_corr_volume_pyramid: maps [planes, channels, h, w] fp16, channels first; src, dst [edges] int64 plane indices; slots [edges]
+ *   int64.  Level 0 of slot slots[e] is V0[p1, p2] = (1/16) sum_c maps[src[e], c, p1] maps[dst[e], c, p2], the products exact in
+ *   fp32, the sum in fp32 by mfma_f32_16x16x32_f16 in an order the tile fixes.  Level l is the mean of the fp32 V0 over the aligned
+ *   2^l x 2^l block of p2, formed by successive 2 x 2 sums ((a + b) + (c + d), rows first) each scaled by 0.25, for block rows
+ *   < h >> l and block columns < w >> l (an odd last row or column is dropped).  Each level is rounded to fp16 once, on its store
+ *   (overflow gives inf).  An edge whose src or dst lies outside [0, planes) (compared in 64 bits) gets zeros in every element of its
+ *   slot at every level and reads nothing; an edge whose slot lies outside [0, capacity) writes nothing; two edges of one call with
+ *   the same slot are undefined.  An edge gives the same bits alone, in any batch and in any slot.  h, w >= 1; h*w must fit int32
+ *   and edges <= 65535; channels must be a positive multiple of 32 up to 1024 (SGR_ERR_CAPACITY otherwise).  edges = 0 is a no-op.
+ * sgr_corr_index_pyramid_forward: coords [edges, h, w, 2] fp32 (x, y) at the scale of level 0; corr [edges, num_levels*rd*rd, h, w]
+ *   fp16: the channels [l*rd*rd, (l+1)*rd*rd) are bit for bit sgr_corr_index_forward(level_l[slots], coords * 2^-l, radius) (the same
+ *   window rule, walk and single rounding).  A level without pixels and an edge whose slot lies outside [0, capacity) give zeros;
+ *   every output element is written.  edges >= 1, edges*h*w must fit int32, radius <= 4 (SGR_ERR_CAPACITY beyond). */
+int sgr_corr_volume_pyramid(const void* maps, const int64_t* src, const int64_t* dst, const int64_t* slots, void* level0, void* level1,
+                            void* level2, void* level3, int32_t planes, int32_t edges, int32_t capacity, int32_t channels, int32_t h,
+                            int32_t w, int32_t num_levels, void* stream);
+int sgr_corr_index_pyramid_forward(const void* level0, const void* level1, const void* level2, const void* level3, const int64_t* slots,
+                                   const float* coords, void* corr, int32_t capacity, int32_t edges, int32_t h, int32_t w, int32_t radius,
+                                   int32_t num_levels, void* stream);
 
 /* The factor graph of the tracker (FactorGraph, thirdparty/glorie_slam/factor_graph.py).  Stated in DESIGN.md section 3, "Factor
  * graph".  Everything is stream-ordered, allocates nothing, synchronises nothing and is bitwise reproducible.

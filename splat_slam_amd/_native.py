@@ -291,6 +291,7 @@ SGR_VIDEO_MAX_FRAMES = 65535
 SGR_FUSE_MAX_FRAMES = 65535
 SGR_CORR_MAX_RADIUS = 1023
 SGR_CORR_PYRAMID_MAX_RADIUS, SGR_CORR_PYRAMID_MAX_LEVELS = 4, 4
+SGR_CORR_VOLUME_CHANNEL_STEP, SGR_CORR_VOLUME_MAX_CHANNELS, SGR_CORR_VOLUME_MAX_EDGES = 32, 1024, 65535
 SGR_GRAPH_MAX_EDGES = 65535
 SGR_GRAPH_MAX_SIDE = 512
 
@@ -394,6 +395,8 @@ SIGNATURES = {
     "sgr_corr_alt_forward": (C.c_int, [_fp, _fp, _fp, _fp] + [C.c_int32] * 8 + [_fp]),
     "sgr_corr_alt_backward": (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp] + [C.c_int32] * 8 + [_fp]),
     "sgr_corr_alt_pyramid_forward": (C.c_int, [_fp] * 8 + [C.c_int32] * 8 + [_fp]),
+    "sgr_corr_volume_pyramid": (C.c_int, [_fp] * 8 + [C.c_int32] * 7 + [_fp]),
+    "sgr_corr_index_pyramid_forward": (C.c_int, [_fp] * 7 + [C.c_int32] * 6 + [_fp]),
     "sgr_graph_reproject": (C.c_int, [_fp, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, C.c_int32, _fp, _fp, _fp, _fp,
                                       _fp]),
     "sgr_graph_select_scratch_bytes": (C.c_size_t, [C.c_int32] * 2),

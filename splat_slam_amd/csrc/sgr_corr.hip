@@ -4,6 +4,7 @@
 //   sgr_corr_index_backward  corr_index_backward: its transpose, every element of volume_grad written once
 //   sgr_corr_alt_forward     altcorr_forward: the same window with the correlations computed on the fly from two feature maps
 //   sgr_corr_alt_backward    altcorr_backward: gradients of that with respect to both feature maps
+//   sgr_corr_index_pyramid_forward  corr_index_forward at every level of a volume pyramid kept in slots (sgr_corr_volume.hip), one launch
 //   sgr_corr_alt_pyramid_forward  altcorr_forward at every level of a feature pyramid in one launch, the frames of each edge read
 //                            through their indices out of an fp16 or fp32 store (the low-memory lookup of FactorGraph.update_lowmem)
 // Layout and measured times: DESIGN.md section 3, "Correlation lookups".  Outputs are indexed x offset first, then y offset.  Sums
@@ -49,18 +50,12 @@ __device__ __forceinline__ Window make_window(float x0, float y0, int r, int h2,
 // One thread per pixel, lanes along x: the stores to each of the rd*rd output planes are coalesced.  The window is walked row
 // by row: each of its (rd+1)^2 elements is loaded once, interpolated along x against its left neighbour, and two consecutive
 // rows give one row of outputs.
+// The window walk of one pixel, shared by corr_index_fwd_kernel and corr_index_pyramid_fwd_kernel: plane [h2,w2] is the pixel's own,
+// out its first output, the rd*rd outputs HW1 elements apart.
 template <typename T, int R>
-__global__ void __launch_bounds__(kThreads) corr_index_fwd_kernel(const T* __restrict__ volume, const float* __restrict__ coords,
-                                                                  T* __restrict__ corr, int P, int HW1, int h2, int w2) {
+__device__ __forceinline__ void index_window(const T* __restrict__ plane, const Window& w, int h2, int w2, T* __restrict__ out, int HW1) {
   constexpr int RD = 2 * R + 1;
-  const int p = blockIdx.x * kThreads + threadIdx.x;
-  if (p >= P) return;
-  const int n = p / HW1, yx = p - n * HW1;
-  const float* cp = coords + (int64_t)n * 2 * HW1 + yx;
-  const Window w = make_window(cp[0], cp[HW1], R, h2, w2);
   const float wx0 = 1.f - w.dx, wy0 = 1.f - w.dy;
-  const T* plane = volume + (int64_t)p * (h2 * w2);
-  T* out = corr + (int64_t)n * (RD * RD) * HW1 + yx;
   float hprev[RD];
 #pragma unroll
   for (int j = 0; j <= RD; ++j) {
@@ -81,6 +76,44 @@ __global__ void __launch_bounds__(kThreads) corr_index_fwd_kernel(const T* __res
       hprev[a] = h[a];
     }
   }
+}
+
+template <typename T, int R>
+__global__ void __launch_bounds__(kThreads) corr_index_fwd_kernel(const T* __restrict__ volume, const float* __restrict__ coords,
+                                                                  T* __restrict__ corr, int P, int HW1, int h2, int w2) {
+  constexpr int RD = 2 * R + 1;
+  const int p = blockIdx.x * kThreads + threadIdx.x;
+  if (p >= P) return;
+  const int n = p / HW1, yx = p - n * HW1;
+  const float* cp = coords + (int64_t)n * 2 * HW1 + yx;
+  const Window w = make_window(cp[0], cp[HW1], R, h2, w2);
+  index_window<T, R>(volume + (int64_t)p * (h2 * w2), w, h2, w2, corr + (int64_t)n * (RD * RD) * HW1 + yx, HW1);
+}
+
+// ---- corr_index over the slots of a volume pyramid: level_l [capacity,h,w,h>>l,w>>l] fp16, slots [E], coords [E,h,w,2] (x, y),
+// corr [E, L*rd*rd, h, w].  blockIdx.y is the level; one thread per (edge, pixel) walks the window of corr_index_fwd_kernel in the
+// plane of slot slots[e] at coords * 2^-l (an exact scaling).  An empty level and a slot outside the store are dead windows: zeros.
+struct SlotLevels {
+  const _Float16* v[4];
+};
+template <int R>
+__global__ void __launch_bounds__(kThreads) corr_index_pyramid_fwd_kernel(SlotLevels lv, const int64_t* __restrict__ slots,
+                                                                          const float* __restrict__ coords, _Float16* __restrict__ corr,
+                                                                          int P, int HW, int h, int w, int capacity, int L) {
+  constexpr int RD = 2 * R + 1;
+  const int p = blockIdx.x * kThreads + threadIdx.x;
+  if (p >= P) return;
+  const int l = blockIdx.y, h2 = h >> l, w2 = w >> l;
+  const int e = p / HW, yx = p - e * HW;
+  const float2 c = *(const float2*)(coords + (int64_t)p * 2);
+  const float scale = 1.f / (float)(1 << l);           // a power of two: coords * scale == coords / 2^l exactly
+  const int64_t slot = slots[e];
+  const bool on = slot >= 0 && slot < capacity && h2 > 0 && w2 > 0;
+  Window win = make_window(c.x * scale, c.y * scale, R, h2, w2);
+  if (!on) win = Window{0, 0, 0.f, 0.f, false};
+  const _Float16* base = l == 0 ? lv.v[0] : l == 1 ? lv.v[1] : l == 2 ? lv.v[2] : lv.v[3];
+  const _Float16* plane = base + (on ? (slot * HW + yx) * ((int64_t)h2 * w2) : 0);
+  index_window<_Float16, R>(plane, win, h2, w2, corr + ((int64_t)e * L + l) * (RD * RD) * HW + yx, HW);
 }
 
 // any radius: every output gathers its own four corners (no per-thread arrays whose size depends on the radius)
@@ -478,6 +511,37 @@ int sgr_corr_alt_pyramid_forward(const void* level0, const void* level1, const v
   else
     hipLaunchKernelGGL((altcorr_pyramid_fwd_kernel<float>), grid, block, lds_bytes(tile), (hipStream_t)stream, lv, src, dst, coords, corr,
                        frames, h, w, channels, radius, num_levels, tile, tiles_per);
+  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "%s launch failed", what);
+}
+
+int sgr_corr_index_pyramid_forward(const void* level0, const void* level1, const void* level2, const void* level3, const int64_t* slots,
+                                   const float* coords, void* corr, int32_t capacity, int32_t edges, int32_t h, int32_t w, int32_t radius,
+                                   int32_t num_levels, void* stream) {
+  const char* what = "corr_index_pyramid_forward";
+  if (!slots || !coords || !corr) return set_error(SGR_ERR_INVALID, "%s: null argument", what);
+  if (num_levels < 1 || num_levels > kMaxPyramidLevels)
+    return set_error(SGR_ERR_INVALID, "%s: num_levels (%d) must lie in [1, %d]", what, num_levels, kMaxPyramidLevels);
+  if (capacity < 1 || edges < 1 || h < 1 || w < 1 || radius < 0)
+    return set_error(SGR_ERR_INVALID, "%s: bad sizes (capacity=%d edges=%d h=%d w=%d radius=%d)", what, capacity, edges, h, w, radius);
+  if (radius > kMaxRegRadius) return set_error(SGR_ERR_CAPACITY, "%s: radius %d exceeds the supported %d", what, radius, kMaxRegRadius);
+  if (!fits_i32((int64_t)edges * h * w)) return set_error(SGR_ERR_CAPACITY, "%s: edges*h*w must fit in int32", what);
+  SlotLevels lv = {{(const _Float16*)level0, (const _Float16*)level1, (const _Float16*)level2, (const _Float16*)level3}};
+  for (int l = 0; l < kMaxPyramidLevels; ++l) {
+    if (l >= num_levels) lv.v[l] = nullptr;
+    else if (!lv.v[l] && (h >> l) > 0 && (w >> l) > 0) return set_error(SGR_ERR_INVALID, "%s: level %d is null", what, l);
+  }
+  const int HW = h * w, P = edges * HW;
+  const dim3 grid((P + kThreads - 1) / kThreads, num_levels), block(kThreads);
+  _Float16* o = (_Float16*)corr;
+  hipStream_t st = (hipStream_t)stream;
+  switch (radius) {
+    case 0: hipLaunchKernelGGL((corr_index_pyramid_fwd_kernel<0>), grid, block, 0, st, lv, slots, coords, o, P, HW, h, w, capacity, num_levels); break;
+    case 1: hipLaunchKernelGGL((corr_index_pyramid_fwd_kernel<1>), grid, block, 0, st, lv, slots, coords, o, P, HW, h, w, capacity, num_levels); break;
+    case 2: hipLaunchKernelGGL((corr_index_pyramid_fwd_kernel<2>), grid, block, 0, st, lv, slots, coords, o, P, HW, h, w, capacity, num_levels); break;
+    case 3: hipLaunchKernelGGL((corr_index_pyramid_fwd_kernel<3>), grid, block, 0, st, lv, slots, coords, o, P, HW, h, w, capacity, num_levels); break;
+    default: hipLaunchKernelGGL((corr_index_pyramid_fwd_kernel<4>), grid, block, 0, st, lv, slots, coords, o, P, HW, h, w, capacity, num_levels); break;
+  }
+  static_assert(kMaxRegRadius == 4, "one case per register radius");
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "%s launch failed", what);
 }
 

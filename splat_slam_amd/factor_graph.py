@@ -20,7 +20,7 @@ stream-ordered.  The matrix is at most 512 x 512 (the DepthVideo buffer limit). 
 import torch
 
 from splat_slam_amd import _native as nat
-from splat_slam_amd.corr import AltCorrBlock, CorrBlock, FusedAltCorrBlock
+from splat_slam_amd.corr import AltCorrBlock, CorrBlock, FusedAltCorrBlock, FusedCorrBlock
 
 __all__ = ["reproject", "select_proximity_edges", "select_backend_edges", "FactorGraph"]
 
@@ -183,8 +183,10 @@ class FactorGraph:
     `add_factors, rm_factors, rm_keyframe, filter_edges, clear_edges, update, update_lowmem, add_neighborhood_factors,
     add_proximity_factors, add_backend_proximity_factors`.  `update_op(net, inp, corr, motn, ii, jj) -> (net, delta, weight, damping,
     upmask)` is any callable with the signature of the reference's update operator; the graph does not contain the network.
-    `corr_impl`: "volume" keeps a CorrBlock per edge (the frontend); "alt" and "alt_fused" keep none and differ only in the
-    operator `update_lowmem` builds (AltCorrBlock, FusedAltCorrBlock).
+    `corr_impl`: "volume" keeps a CorrBlock per edge (the frontend); "volume_fused" keeps one FusedCorrBlock over `video.fmaps`
+    (max_factors + 16 slots, 64 when max_factors is unbounded; it grows when it must), adds edges into free slots, drops them from
+    its slot list and looks every level up in one launch; "alt" and "alt_fused" keep none and differ only in the operator
+    `update_lowmem` builds (AltCorrBlock, FusedAltCorrBlock).
 
     New edges that are already active or inactive are dropped, on the device (keys i * 2^31 + j, torch.isin).
 
@@ -247,6 +249,11 @@ class FactorGraph:
                 corr = CorrBlock(self.video.fmaps[ii, 0].to(self.device).unsqueeze(0),
                                  self.video.fmaps[jj, second].to(self.device).unsqueeze(0))
             self.corr = corr if self.corr is None else self.corr.cat(corr)
+        elif self.corr_impl == "volume_fused":
+            if self.corr is None:
+                self.corr = FusedCorrBlock(self.video.fmaps, capacity=self.max_factors + 16 if self.max_factors > 0 else 64)
+            self.corr.add(ii, jj)
+        if self.corr_impl in ("volume", "volume_fused"):
             inp = self.video.inps[ii].to(self.device).unsqueeze(0)
             self.inp = inp if self.inp is None else torch.cat([self.inp, inp], 1)
         target = reproject(self.video.poses, self.video.disps, self.video.intrinsics, ii.contiguous(), jj.contiguous())[0][None]
@@ -268,6 +275,8 @@ class FactorGraph:
         self.ii, self.jj, self.age = self.ii[keep], self.jj[keep], self.age[keep]
         if self.corr_impl == "volume" and self.corr is not None:
             self.corr = self.corr[keep]
+        elif self.corr_impl == "volume_fused" and self.corr is not None:
+            self.corr = self.corr[keep, self.ii.shape[0]]
         if self.net is not None:
             self.net = self.net[:, keep]
         if self.inp is not None:

@@ -5,8 +5,9 @@ FactorGraph.update, dropping the newest keyframe again when it is too close to t
     Frontend(net, video, cfg)
         net: a DroidNet (net.update); video: a DepthVideo; cfg: the reference's dict, read at cfg["device"], cfg["tracking"][max_age,
         warmup, beta] and cfg["tracking"]["frontend"][nms, keyframe_thresh, window, thresh, radius, max_factors, enable_loop]
-        (and what Backend reads).  Attributes as in the reference: video, update_op, t1, is_initialized, max_age, iters1 = 8,
-        iters2 = 4, warmup, beta, frontend_*, enable_loop, loop_closing (a Backend), graph (corr_impl "volume"), and after the
+        (and what Backend reads).  One more keyword, corr_impl="volume": the graph's correlation operator, "volume" (a CorrBlock
+        per batch of edges) or "volume_fused" (one FusedCorrBlock over video.fmaps).  Attributes as in the reference: video, update_op, t1, is_initialized, max_age, iters1 = 8,
+        iters2 = 4, warmup, beta, frontend_*, enable_loop, loop_closing (a Backend), graph, and after the
         initialisation last_pose, last_disp, last_time.
     frontend()
         counter == warmup and not initialised: neighbourhood edges (r = 3), 8 updates, proximity edges (rad 2, nms 2, remove=False),
@@ -31,7 +32,9 @@ __all__ = ["Frontend"]
 
 
 class Frontend:
-    def __init__(self, net, video, cfg):
+    def __init__(self, net, video, cfg, corr_impl="volume"):
+        if corr_impl not in ("volume", "volume_fused"):
+            raise ValueError(f"Frontend: corr_impl must be 'volume' or 'volume_fused', got {corr_impl!r}")
         self.video, self.update_op = video, net.update
         self.t1 = 0                                     # end of the local optimisation window
         self.is_initialized = False
@@ -43,7 +46,7 @@ class Frontend:
         self.frontend_thresh, self.frontend_radius, self.frontend_max_factors = fe["thresh"], fe["radius"], fe["max_factors"]
         self.enable_loop = fe["enable_loop"]
         self.loop_closing = Backend(net, video, cfg)
-        self.graph = FactorGraph(video, net.update, device=cfg["device"], corr_impl="volume", max_factors=self.frontend_max_factors)
+        self.graph = FactorGraph(video, net.update, device=cfg["device"], corr_impl=corr_impl, max_factors=self.frontend_max_factors)
 
     def _refine(self):
         for itr in range(self.iters2):

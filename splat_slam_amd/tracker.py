@@ -7,6 +7,8 @@ DESIGN.md section 3, "Tracker".
         cfg["tracking"]["frontend"][window, enable_online_ba], cfg["tracking"]["backend"]["ba_freq"], cfg["mapping"]["every_keyframe"]
         (and what Frontend and Backend read); net: a DroidNet; video: a DepthVideo.  Attributes: motion_filter, frontend, online_ba.
         One more keyword, mono_depth=None: the mono-depth callable that is passed on to MotionFilter.
+        frontend_corr_impl="volume": the correlation operator of the frontend's graph, passed on to Frontend ("volume_fused": one
+        FusedCorrBlock over video.fmaps).  The motion filter keeps CorrBlock: its one edge is not in the video.
     tracker.run(stream)
         stream: len(stream), stream[i] -> (timestamp, image [1,3,H,W] in [0, 1], ...), stream.get_intrinsic() -> [4].
         Per frame: motion_filter.track(timestamp, image, intrinsic), then frontend().  When the index of the newest keyframe has
@@ -27,7 +29,7 @@ __all__ = ["Tracker"]
 
 
 class Tracker:
-    def __init__(self, cfg, net, video, on_keyframe=None, only_tracking=False, mono_depth=None):
+    def __init__(self, cfg, net, video, on_keyframe=None, only_tracking=False, mono_depth=None, frontend_corr_impl="volume"):
         self.cfg, self.net, self.video, self.device = cfg, net, video, cfg["device"]
         self.on_keyframe, self.only_tracking = on_keyframe, only_tracking
         tr = cfg["tracking"]
@@ -36,7 +38,8 @@ class Tracker:
         self.motion_filter = MotionFilter(net, video, thresh=tr["motion_filter"]["thresh"], device=self.device, **prior)
         self.enable_online_ba = tr["frontend"]["enable_online_ba"]
         self.every_kf = cfg["mapping"]["every_keyframe"]
-        self.frontend = Frontend(net, video, cfg)
+        front = {} if frontend_corr_impl == "volume" else {"corr_impl": frontend_corr_impl}     # the default builds it exactly as before
+        self.frontend = Frontend(net, video, cfg, **front)
         self.online_ba = Backend(net, video, cfg)
         self.ba_freq = tr["backend"]["ba_freq"]
 

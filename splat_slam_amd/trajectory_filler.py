@@ -6,7 +6,8 @@ them with the update operator.  Stated in DESIGN.md section 3, "Tracker".
         t0 = #{ts <= t} - 1, t1 = t0 + 1 where t0 < N - 1 and t0 elsewhere: a timestamp after the last keyframe gets t0 = t1 = N - 1, one
         before the first gets t0 = -1, t1 = 0.  Plain torch on the device of ts.
     PoseTrajectoryFiller(net, video, device="cuda")
-        net: a DroidNet (net.fnet, net.update); video: a DepthVideo with N = video.counter.value keyframes
+        net: a DroidNet (net.fnet, net.update); video: a DepthVideo with N = video.counter.value keyframes.  One more keyword,
+        corr_impl="volume": the correlation operator of the graph of each block of frames, "volume" or "volume_fused" (FactorGraph)
     filler.interpolate(timestamps) -> [M,7]
         exp(log(P[t1] * P[t0]^-1) / dt * (t - ts[t0])) * P[t0] with dt = ts[t1] - ts[t0] + 1e-3, through lietorch.SE3: at a keyframe's
         timestamp exactly that keyframe's pose; after the last keyframe (t0 = t1) the last pose up to the rounding of P * P^-1, which
@@ -40,8 +41,10 @@ def bracket(ts, tt):
 
 
 class PoseTrajectoryFiller:
-    def __init__(self, net, video, device="cuda"):
-        self.fnet, self.update = net.fnet, net.update
+    def __init__(self, net, video, device="cuda", corr_impl="volume"):
+        if corr_impl not in ("volume", "volume_fused"):
+            raise ValueError(f"PoseTrajectoryFiller: corr_impl must be 'volume' or 'volume_fused', got {corr_impl!r}")
+        self.fnet, self.update, self.corr_impl = net.fnet, net.update, corr_impl
         self.count = 0
         self.video, self.device = video, device
 
@@ -78,7 +81,7 @@ class PoseTrajectoryFiller:
         self.video.counter.value += M
         intrinsics = (intrinsic.to(self.device) / float(self.video.down_scale)).expand(M, 4)
         self.video[N:N + M] = (tt, inputs[:, 0], Gs, 1, None, intrinsics, fmap)
-        graph = FactorGraph(self.video, self.update, device=self.device)
+        graph = FactorGraph(self.video, self.update, device=self.device, corr_impl=self.corr_impl)
         frames = torch.arange(N, N + M, device=self.device)
         graph.add_factors(t0, frames)
         graph.add_factors(t1, frames)
