@@ -85,6 +85,10 @@ extern "C" {
 
 #define SGR_ABI_VERSION 10
 
+/* In front of a pointer to a scalar: it addresses HOST memory (every unmarked pointer to a scalar or to void is a device pointer
+ * unless its comment says otherwise).  Expands to nothing; the Python binding reads it to give the pointer its element type. */
+#define SGR_HOST
+
 typedef enum SgrStatus {
   SGR_OK = 0,
   SGR_ERR_INVALID = -1,     /* bad argument (null pointer, inconsistent option set, ...)            */
@@ -191,7 +195,7 @@ size_t sgr_scratch_bytes(int32_t num_gaussians, int32_t image_height, int32_t im
  * -- the synchronous form fails with SGR_ERR_INVALID.  A view whose overflow word is non-zero contributes zeros to
  * sgr_backward / sgr_map_* gradients instead of sums over truncated lists. */
 int sgr_forward(const SgrSettings* settings, const SgrInputs* in, const SgrOutputs* out,
-                const SgrWorkspace* ws, int64_t* num_rendered_host, void* stream);
+                const SgrWorkspace* ws, SGR_HOST int64_t* num_rendered_host, void* stream);
 
 int sgr_backward(const SgrSettings* settings, const SgrInputs* in, const int32_t* radii,
                  const SgrGradOutputs* grad_out, const SgrGradInputs* grad_in,
@@ -222,7 +226,7 @@ int sgr_densify_stats(int64_t n, const float* dL_dmeans2D, const int32_t* radii,
                       float* stat_max_radii, void* stream);
 
 /* Synchronous read-back of (pair count, overflow flag) from a saved block produced by sgr_forward. */
-int sgr_query(const void* saved, int64_t* num_rendered_host, int32_t* overflow_host, void* stream);
+int sgr_query(const void* saved, SGR_HOST int64_t* num_rendered_host, SGR_HOST int32_t* overflow_host, void* stream);
 
 /* The whole 64-byte header of a saved block, synchronously: uint32 words [0] pair count R the workspace must hold (the larger of
  * pairs binned and partial slots reserved), [1] overflow flag, [2] pairs sorted, [3] visible Gaussians, [4] tiles with more
@@ -231,7 +235,7 @@ int sgr_query(const void* saved, int64_t* num_rendered_host, int32_t* overflow_h
  * [13] STICKY: the largest [0] of any of those forwards -- [1] only describes the LAST forward, and a span of sgr_map_run puts dozens
  * of forwards through one workspace between two host checks -- [14] internal (a flag between two blocks of the binning kernel: zero
  * whenever no forward is running), [15] zero. */
-int sgr_query_header(const void* saved, uint32_t words_host[16], void* stream);
+int sgr_query_header(const void* saved, SGR_HOST uint32_t words_host[16], void* stream);
 
 /* Asynchronous variant: enqueues a 64-byte copy of the same header into PINNED host memory on `stream`.
  * The caller pre-sets word 15 to a non-zero sentinel and knows the copy has landed when it reads 0 there: a later call can
@@ -243,7 +247,7 @@ int sgr_header_to_host(const void* saved, void* pinned_host64, void* stream);
  *   stats[2] = R_eff = sum over tiles of min(list length, last contributor): pairs the blend kernels walk
  *   stats[3] = number of non-empty 8x8 tiles */
 int sgr_query_stats(const SgrWorkspace* ws, int32_t num_gaussians, int32_t image_height, int32_t image_width,
-                    const int32_t* radii, int64_t stats_host[4], void* stream);
+                    const int32_t* radii, SGR_HOST int64_t stats_host[4], void* stream);
 /* The fp32 view-space depth of every Gaussian with radii > 0 as the forward computed it (0 elsewhere) -- the bit pattern
  * that orders the splats of a tile.  Parity tooling: lets a comparison break depth near-ties (equal to the last ulp) the way
  * this forward did.  depth_out: device [N]. */
@@ -252,7 +256,7 @@ int sgr_query_depth_keys(const SgrWorkspace* ws, int32_t num_gaussians, int32_t 
 /* Histogram of the per-tile list lengths the blend kernels walk (same synchronous, accounting-only use):
  * bins 0, 1-4, 5-8, 9-16, 17-32, 33-64, 65-256, >256 splats. */
 int sgr_query_list_histogram(const SgrWorkspace* ws, int32_t num_gaussians, int32_t image_height, int32_t image_width,
-                             int64_t hist_host[8], void* stream);
+                             SGR_HOST int64_t hist_host[8], void* stream);
 
 /* Run-time options of the library (process-wide; no reference counterpart).
  *   SGR_OPT_FUSED_BLEND (default 1): sgr_map_views / sgr_map_step / sgr_map_run composite a tile, evaluate the mapping loss
@@ -284,7 +288,7 @@ int sgr_get_option(int32_t option);
  * kind since the last read, and resets them. Events are recorded on the stream the kernel is launched on. */
 #define SGR_PROFILE_KINDS 7
 int sgr_profile_enable(uint32_t kind_mask);
-int sgr_profile_read(float ms_host[SGR_PROFILE_KINDS], int64_t launches_host[SGR_PROFILE_KINDS]);
+int sgr_profile_read(SGR_HOST float ms_host[SGR_PROFILE_KINDS], SGR_HOST int64_t launches_host[SGR_PROFILE_KINDS]);
 
 /* Fused mapping loss (slam_utils.py:71-105): loss = alpha*mean|m*(e^a*I+b) - m*gt| + (1-alpha)*mean|md*D - md*gtD|
  * with m = (sum_c gt > rgb_boundary_threshold), md = (gtD > 0.01).  Writes loss[1] and the four gradients
@@ -402,16 +406,16 @@ int sgr_surface_sample(int32_t V, int32_t F, const float* vertices, const int32_
  * the nearest target point and idx = its index (ties: the smallest index); where that distance exceeds max_dist (INFINITY: no
  * limit) dist = INFINITY and idx = -1. */
 size_t sgr_nn_grid_bytes(int32_t n);
-int sgr_nn_grid_build(int32_t n, const float* points, const float* transform, void* grid, size_t grid_bytes, void* stream);
-int sgr_nn_query(int32_t n, const void* grid, size_t grid_bytes, int32_t nq, const float* query, const float* transform, float max_dist,
-                 float* dist, int32_t* idx, void* stream);
+int sgr_nn_grid_build(int32_t n, const float* points, SGR_HOST const float* transform, void* grid, size_t grid_bytes, void* stream);
+int sgr_nn_query(int32_t n, const void* grid, size_t grid_bytes, int32_t nq, const float* query, SGR_HOST const float* transform,
+                 float max_dist, float* dist, int32_t* idx, void* stream);
 /* Fixed-order fp64 reductions (per-workgroup partials in `scratch` of sgr_eval_reduce_bytes() bytes, then one ordered pass; no
  * float atomics).  sgr_icp_accumulate: over the sources with idx >= 0, p = transform * source (as sgr_nn_query forms it) and
  * q = target[idx]: sums[17] = count, sum |p - q|^2, sum p (3), sum q (3), sum p q^T (9, row-major).  sgr_cloud_metrics:
  * out[4] = sum dist_a, #(dist_a < thresh), sum dist_b, #(dist_b < thresh). */
 size_t sgr_eval_reduce_bytes(void);
-int sgr_icp_accumulate(int32_t n, const float* source, const float* transform, const int32_t* idx, int32_t n_target, const float* target,
-                       double* sums, void* scratch, size_t scratch_bytes, void* stream);
+int sgr_icp_accumulate(int32_t n, const float* source, SGR_HOST const float* transform, const int32_t* idx, int32_t n_target,
+                       const float* target, double* sums, void* scratch, size_t scratch_bytes, void* stream);
 int sgr_cloud_metrics(int32_t na, const float* dist_a, int32_t nb, const float* dist_b, float thresh, double* out, void* scratch,
                       size_t scratch_bytes, void* stream);
 
@@ -463,8 +467,8 @@ int sgr_gaussian_adam_step(int64_t n, const SgrAdamGroup groups[5], float beta1,
  * row0[k] <= i < row1[k] only; its four pointers still address ROW 0 of the (virtual) full arrays and are only
  * dereferenced inside that range, so `grad` may point into a rank-local shard buffer.  The isotropy term is normalised by
  * n_total (the whole map).  No activations are written: the caller re-activates after its all-gather. */
-int sgr_gaussian_adam_shard(int64_t n_total, const SgrAdamGroup groups[5], const int64_t row0[5], const int64_t row1[5],
-                            float beta1, float beta2, float eps, float iso_weight, void* stream);
+int sgr_gaussian_adam_shard(int64_t n_total, const SgrAdamGroup groups[5], SGR_HOST const int64_t row0[5],
+                            SGR_HOST const int64_t row1[5], float beta1, float beta2, float eps, float iso_weight, void* stream);
 
 /* One mapping-loop view: render, mapping loss and its gradient, backward (src/mapper.py:426-456 for one viewpoint).
  * sgr_map_views runs the sequence  sgr_forward(async) -> sgr_mapping_loss -> sgr_backward  for `num_views` views
@@ -558,10 +562,10 @@ typedef struct SgrMapRun {
   int32_t pool_size;
   int32_t picks_per_iter;
   const SgrMapView* pool;
-  const int32_t* picks;         /* host, [num_iters * picks_per_iter] */
-  const float* lr0;             /* host, [num_iters] or NULL (keep adam_groups[0].lr) */
+  SGR_HOST const int32_t* picks;         /* host, [num_iters * picks_per_iter] */
+  SGR_HOST const float* lr0;             /* host, [num_iters] or NULL (keep adam_groups[0].lr) */
   SgrAdamGroup* adam_groups;    /* host, [5] or NULL */
-  const int32_t* pool_exp_row;  /* host, [pool_size] or NULL */
+  SGR_HOST const int32_t* pool_exp_row;  /* host, [pool_size] or NULL */
   int32_t n_touched_last_only;  /* != 0: n_touched is only produced by the last iteration (nobody can observe the others) */
   const SgrWorkspace* pick_ws;  /* host, [picks_per_iter] or NULL.  Non-NULL: pick j of every iteration renders in pick_ws[j]
                                    instead of its pool entry's own workspace -- a map holds hundreds of keyframes, an iteration
@@ -647,6 +651,7 @@ int sknn_dist2(const float* xyz, int32_t n, float* mean_dist2, void* scratch, si
  * window is limited to 512 frames (SGR_ERR_CAPACITY beyond).  A reduced system that is not positive definite gives dx = 0 and the
  * step goes on.  When K differs from the number of distinct depth frames found on the device, nothing is updated and dx, dz
  * are NaN.  motion_only solves the pose blocks alone (dz untouched, may be NULL); depth_only leaves the poses as they are. */
+#define SGR_DBA_MAX_WINDOW 512              /* sgr_dba_ba: frames t1 - t0 of the window */
 typedef struct SgrDbaProblem {
   float* poses;                /* [num_poses, 7], updated */
   int32_t num_poses;
@@ -739,6 +744,7 @@ int sgr_dspo_ba(const SgrDspoProblem* problem, void* scratch, size_t scratch_byt
  * scratch: sgr_video_scratch_bytes(num, ht, wd) bytes, 16-byte aligned (0 = unsupported sizes). */
 #define SGR_VIDEO_MASK_F32 0
 #define SGR_VIDEO_MASK_F16 1
+#define SGR_VIDEO_MAX_FRAMES 65535          /* sgr_video_*: `num` of one call */
 int sgr_video_cvx_upsample(const float* disps, int32_t num_frames, int32_t ht, int32_t wd, const int64_t* inds, int32_t num,
                            const void* mask, int32_t mask_kind, float* disps_up, void* stream);
 int sgr_video_depth_thresh(const float* disps, int32_t num_frames, int32_t ht, int32_t wd, const int64_t* inds, int32_t num, float rel,
@@ -770,6 +776,7 @@ int sgr_video_valid_mask(const float* poses, const float* disps, int32_t num_fra
  *   scale and shift are left unwritten.  A slot whose index lies outside [0, num_frames) gets invalid = 1 and a depth of zeros.  A frame
  *   gives the same bits alone and in any batch.
  * scratch: sgr_fuse_scratch_bytes(num, ht, wd) bytes, 16-byte aligned, serves either call (0 = unsupported sizes). */
+#define SGR_FUSE_MAX_FRAMES 65535           /* sgr_fuse_*: `num` of one call */
 size_t sgr_fuse_scratch_bytes(int32_t num, int32_t ht, int32_t wd);
 int sgr_fuse_prepare(const float* mono, int32_t num, int32_t ht, int32_t wd, float* mono_filled, uint8_t* eroded, void* scratch,
                      size_t scratch_bytes, void* stream);
@@ -788,6 +795,12 @@ int sgr_fuse_depth(const float* disps_up, const uint8_t* valid_depth_mask, const
  * corr, corr_grad [batch,num,rd*rd,h1,w1], all fp32; channels is a positive multiple of 4. */
 #define SGR_CORR_F32 0
 #define SGR_CORR_F16 1
+#define SGR_CORR_MAX_RADIUS 1023            /* sgr_corr_index_*, sgr_corr_alt_forward / _backward */
+#define SGR_CORR_PYRAMID_MAX_RADIUS 4       /* the pyramid lookups: sgr_corr_alt_pyramid_forward, sgr_corr_index_pyramid_forward */
+#define SGR_CORR_PYRAMID_MAX_LEVELS 4       /* num_levels of the pyramid calls (the level0 .. level3 arguments) */
+#define SGR_CORR_VOLUME_CHANNEL_STEP 32     /* sgr_corr_volume_pyramid: channels is a positive multiple of this ... */
+#define SGR_CORR_VOLUME_MAX_CHANNELS 1024   /* ... up to this */
+#define SGR_CORR_VOLUME_MAX_EDGES 65535     /* sgr_corr_volume_pyramid: edges of one call */
 int sgr_corr_index_forward(const void* volume, const float* coords, void* corr, int32_t dtype, int32_t batch, int32_t h1, int32_t w1,
                            int32_t h2, int32_t w2, int32_t radius, void* stream);
 int sgr_corr_index_backward(const float* coords, const void* corr_grad, void* volume_grad, int32_t dtype, int32_t batch, int32_t h1,
@@ -847,6 +860,8 @@ int sgr_corr_index_pyramid_forward(const void* level0, const void* level1, const
  * counts[1] the number of loop pairs among them (loop != 0); nothing is written past cap.  ii_old, jj_old [num_old]: the existing
  * edges, of any value.  thresh is finite, 0 <= nms <= 512, 0 <= rad.
  * scratch: sgr_graph_select_scratch_bytes(rows, cols) bytes, 16-byte aligned (0 = unsupported sizes). */
+#define SGR_GRAPH_MAX_EDGES 65535           /* sgr_graph_reproject: edges of one call */
+#define SGR_GRAPH_MAX_SIDE 512              /* sgr_graph_select_*: rows and columns of the distance window, and nms */
 int sgr_graph_reproject(const float* poses, int32_t num_poses, const float* disps, int32_t num_frames, int32_t ht, int32_t wd,
                         const float* intrinsics, const int64_t* ii, const int64_t* jj, int32_t num_edges, const float* target,
                         float* coords, float* valid, float* motn, void* stream);
@@ -972,6 +987,8 @@ int sgr_update_forward(const SgrUpdateWeights* weights, const SgrUpdateCall* cal
 #define SGR_ENCODER_ACT_RELU 1
 #define SGR_ENCODER_ACT_SPLIT 2
 #define SGR_ENCODER_LAYERS 16
+#define SGR_ENCODER_LAUNCHES_NONE 17        /* launches of sgr_encoder_forward with norm = SGR_ENCODER_NORM_NONE ... */
+#define SGR_ENCODER_LAUNCHES_INSTANCE 32    /* ... and with SGR_ENCODER_NORM_INSTANCE */
 typedef struct SgrEncoderConv {
   const void* src;
   int32_t src_stride, cin, ksize, stride;
@@ -1003,8 +1020,8 @@ typedef struct SgrEncoderCall {
   int32_t split, first_launch, last_launch;
 } SgrEncoderCall;
 size_t sgr_encoder_scratch_bytes(int32_t n, int32_t H, int32_t W, int32_t out_dim, int32_t norm);
-int sgr_encoder_pack(const SgrUpdateTensor* src, int32_t n, int32_t H, int32_t W, const float* mean, const float* std_, void* dst,
-                     void* stream);
+int sgr_encoder_pack(const SgrUpdateTensor* src, int32_t n, int32_t H, int32_t W, SGR_HOST const float* mean,
+                     SGR_HOST const float* std_, void* dst, void* stream);
 int sgr_encoder_conv(const SgrEncoderConv* conv, void* stream);
 int sgr_encoder_forward(const SgrEncoderWeights* weights, const SgrEncoderCall* call, void* scratch, size_t scratch_bytes, void* stream);
 
@@ -1279,10 +1296,10 @@ typedef struct SgrLpipsCall {
   int32_t first_launch, last_launch;
 } SgrLpipsCall;
 size_t sgr_lpips_scratch_bytes(int32_t n, int32_t H, int32_t W);
-int sgr_lpips_pack(int32_t n, const SgrMetricFrame* frames, int32_t H, int32_t W, const float* shift, const float* scale, void* dst,
-                   void* stream);
-int sgr_lpips_pack_pairs(const float* img0, const float* img1, int32_t n, int32_t H, int32_t W, int32_t normalize, const float* shift,
-                         const float* scale, void* dst, void* stream);
+int sgr_lpips_pack(int32_t n, const SgrMetricFrame* frames, int32_t H, int32_t W, SGR_HOST const float* shift,
+                   SGR_HOST const float* scale, void* dst, void* stream);
+int sgr_lpips_pack_pairs(const float* img0, const float* img1, int32_t n, int32_t H, int32_t W, int32_t normalize,
+                         SGR_HOST const float* shift, SGR_HOST const float* scale, void* dst, void* stream);
 int sgr_lpips_conv(const SgrLpipsConv* conv, void* stream);
 int sgr_lpips_maxpool(const void* src, int32_t n, int32_t h, int32_t w, int32_t channels, void* dst, void* stream);
 int sgr_lpips_distance(const void* maps, int32_t n, int32_t P, int32_t C, const float* weight, float* partials, float* per_pixel,

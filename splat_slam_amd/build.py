@@ -63,6 +63,11 @@ DROPIN_SRC = os.path.join(DROPIN_DIR, "csrc", "dgr_native.cpp")
 DROPIN_LIB = os.path.join(DROPIN_DIR, "_dgr.so")
 
 
+def host_compiler():
+    """The compiler of everything that is host code only (the drop-in extension; the ABI test's layout probe)."""
+    return os.environ.get("CXX", "g++")
+
+
 def dropin_needs_build():
     if not os.path.exists(DROPIN_LIB):
         return True
@@ -80,7 +85,7 @@ def build_dropin_ext(force=False, verbose=True):
     import torch
     from torch.utils import cpp_extension as ce
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    cxx = os.environ.get("CXX", "g++")
+    cxx = host_compiler()
     # (torch ships the pybind11 headers it was built with under its own include path: no separate pybind11 package needed)
     inc = ce.include_paths() + [sysconfig.get_paths()["include"], os.path.join(rocm, "include")]
     tlib = ce.library_paths()[0]

@@ -22,8 +22,8 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kMaxRadius = 1023;            // keeps floor(x0) - radius + i far inside int32 behind the guard below
-constexpr int kMaxRegRadius = 4;            // corr_index_forward keeps a window row in registers up to here (the network's is 3)
+constexpr int kMaxRadius = SGR_CORR_MAX_RADIUS;    // keeps floor(x0) - radius + i far inside int32 behind the guard below
+constexpr int kMaxRegRadius = SGR_CORR_PYRAMID_MAX_RADIUS;   // corr_index_forward keeps a window row in registers up to here (the network's is 3)
 constexpr int kAltTile = 64;                // altcorr_forward: pixels of one workgroup = one coalesced 256-byte store per output plane
 constexpr size_t kAltLdsLimit = 60 * 1024;
 
@@ -281,7 +281,7 @@ __global__ void __launch_bounds__(kThreads) altcorr_bwd_kernel(const float* __re
 }
 
 // ---- altcorr over a pyramid: levels[l] [F,H>>l,W>>l,C] (fp16 or fp32), src, dst [E], coords [E,H,W,2], corr [E,L*rd*rd,H,W]
-constexpr int kMaxPyramidLevels = 4;
+constexpr int kMaxPyramidLevels = SGR_CORR_PYRAMID_MAX_LEVELS;
 constexpr size_t kPyramidLdsTarget = 32 * 1024;     // the output tile is halved until a workgroup needs no more than this
 
 struct PyramidLevels {

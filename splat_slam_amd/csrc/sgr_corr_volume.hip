@@ -32,10 +32,11 @@ typedef __attribute__((ext_vector_type(4))) float floatx4;
 constexpr int kThreads = 256;
 constexpr int kP1 = 64;                     // pixels of map 1 per workgroup: four B tiles
 constexpr int kPatchRows = 8, kPatchCols = 64, kPos = kPatchRows * kPatchCols;      // the patch of map 2: 32 A tiles
-constexpr int kBK = 32;                     // one MFMA k step
+constexpr int kBK = SGR_CORR_VOLUME_CHANNEL_STEP;     // one MFMA k step
 constexpr int kRow = kBK + 8;               // halfs per LDS row of the staged operands (80 bytes: fragment reads spread over the banks)
-constexpr int kMaxLevels = 4;
-constexpr int kMaxChannels = 1024;
+constexpr int kMaxLevels = SGR_CORR_PYRAMID_MAX_LEVELS;
+constexpr int kMaxChannels = SGR_CORR_VOLUME_MAX_CHANNELS;
+constexpr int kMaxEdges = SGR_CORR_VOLUME_MAX_EDGES;       // a grid dimension
 constexpr int kStride0 = kPos + 4, kStride1 = kPos / 4 + 4, kStride2 = kPos / 16 + 1;   // floats per p1 of the epilogue's level images
 constexpr int kStageBytes = (kPos + kP1) * kRow * 2;
 constexpr int kEpiBytes = 16 * (kStride0 + kStride1 + kStride2) * 4;
@@ -242,8 +243,8 @@ int sgr_corr_volume_pyramid(const void* maps, const int64_t* src, const int64_t*
     return set_error(SGR_ERR_INVALID, "%s: bad sizes (planes=%d edges=%d capacity=%d h=%d w=%d)", what, planes, edges, capacity, h, w);
   if (channels < kBK || channels % kBK || channels > kMaxChannels)
     return set_error(SGR_ERR_CAPACITY, "%s: channels (%d) must be a positive multiple of %d up to %d", what, channels, kBK, kMaxChannels);
-  if ((int64_t)h * w > INT32_MAX - kPos || edges > 65535)
-    return set_error(SGR_ERR_CAPACITY, "%s: h*w must fit in int32 and edges (%d) must not exceed 65535", what, edges);
+  if ((int64_t)h * w > INT32_MAX - kPos || edges > kMaxEdges)
+    return set_error(SGR_ERR_CAPACITY, "%s: h*w must fit in int32 and edges (%d) must not exceed %d", what, edges, kMaxEdges);
   VolumeLevels lv = {{(half_t*)level0, (half_t*)level1, (half_t*)level2, (half_t*)level3}};
   bool vec = aligned16(maps);
   for (int l = 0; l < kMaxLevels; ++l) {

@@ -26,7 +26,7 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr float kMinDepth = 0.25f;          // MIN_DEPTH of the reference
 constexpr float kSensorAlpha = 0.05f;       // weight of the depth-sensor prior where disps_sens > 0
-constexpr int kMaxWindow = 512;             // t1 - t0: reduced system of at most 3072 x 3072 (fp64)
+constexpr int kMaxWindow = SGR_DBA_MAX_WINDOW;     // t1 - t0: reduced system of at most 3072 x 3072 (fp64)
 constexpr int kMaxEdges = 65535 - kMaxWindow;   // the slot launch spans T + E workgroup rows
 constexpr int kNb = 64;                     // Cholesky block
 constexpr int kHs = 4 * 36 + 12;            // per edge: Hii, Hij, Hji, Hjj (6x6 each), vi, vj

@@ -22,7 +22,7 @@ namespace {
 
 using dba::frame_ok;
 
-constexpr int kMaxNum = 65535;              // frames per call (a grid dimension)
+constexpr int kMaxNum = SGR_FUSE_MAX_FRAMES;       // frames per call (a grid dimension)
 constexpr long long kMaxPixels = 1LL << 28;
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }

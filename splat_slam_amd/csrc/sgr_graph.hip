@@ -23,7 +23,7 @@ using dba::frame_ok;
 constexpr int kThreads = 256;
 constexpr float kMinDepth = 0.2f;           // MIN_DEPTH of projective_ops.py; the projection replaces z below half of it by 1
 constexpr float kMotionClamp = 64.f;
-constexpr int kMaxEdges = 65535;            // a grid dimension
+constexpr int kMaxEdges = SGR_GRAPH_MAX_EDGES;      // a grid dimension
 
 inline int blocks(long long n, int per = kThreads) { return (int)((n + per - 1) / per); }
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(kThreads) reproject_kernel(int nv, int P, int 
 // ================================================================================================================================
 
 constexpr int kSelThreads = 1024;
-constexpr int kMaxSide = 512;
+constexpr int kMaxSide = SGR_GRAPH_MAX_SIDE;
 constexpr int kDigits = 256;
 constexpr int kLoopGap = 20;                // a loop edge joins frames more than this apart
 enum { kFrontend = 0, kBackend = 1, kBackendLoop = 2 };

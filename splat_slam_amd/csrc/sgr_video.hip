@@ -26,7 +26,7 @@ using dba::frame_ok;
 constexpr int kThreads = 256;
 constexpr int kSub = 8;                     // upsampling factor: 8 x 8 outputs per coarse pixel
 constexpr int kMaskChannels = 9 * kSub * kSub;
-constexpr int kMaxNum = 65535;              // frames per call (a grid dimension, and the limit of sgr_dba_depth_filter)
+constexpr int kMaxNum = SGR_VIDEO_MAX_FRAMES;      // frames per call (a grid dimension, and the limit of sgr_dba_depth_filter)
 
 inline int blocks(long long n, int per = kThreads) { return (int)((n + per - 1) / per); }
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
