@@ -1,5 +1,6 @@
-"""What the networks on the MFMA convolution kernels share on the Python side (update_op, encoder, resnetv2, vit, mono_depth): the packing
-of weights and biases, the tensor record, the current stream, the closed-form synthetic weights and the scratch cache."""
+"""What the networks on the MFMA convolution kernels share on the Python side (update_op, encoder, resnetv2, vit, dpt_decoder, lpips,
+mono_depth): the packing of weights and biases, the tensor record, the tensor and device checks, the current stream, the closed-form
+synthetic weights, the scratch cache and the scaffold of a forward call."""
 import ctypes as C
 
 import numpy as np
@@ -33,6 +34,27 @@ def pack_bias(b, cout, device, row_pad=1):
 
 def stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
+
+
+F16_F32 = (torch.float16, torch.float32)
+
+
+def gpu_tensor(what, name, t, dtypes, dtype_text=None):
+    """t if it is a GPU tensor of one of dtypes, else RuntimeError under the caller's name `what`; dtype_text: how the caller's message
+    names the dtypes ("fp16 or fp32"), by default the tuple itself"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{what} (MI355X build): {name} must be a GPU tensor; there is no CPU path")
+    if t.dtype not in dtypes:
+        raise RuntimeError(f"{what}: {name} must be {dtype_text or f'one of {dtypes}'}, got {t.dtype}")
+    return t
+
+
+def network_device(device, what, noun):
+    """the device a network lives on: cuda only, the index filled in; noun: what the module calls its network in the message"""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"{what} (MI355X build): the {noun} lives on a GPU; there is no CPU path")
+    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
 
 
 def tensor_desc(t):
@@ -73,15 +95,26 @@ class ScratchCache:
     def __init__(self):
         self._bufs = {}
 
-    def get(self, key, device, nbytes_of, unsupported):
-        """nbytes_of() sizes a missing buffer; 0 raises RuntimeError(unsupported)"""
+    def get(self, key, device, nbytes_of, unsupported, grow=False):
+        """nbytes_of() sizes a missing buffer; 0 raises RuntimeError(unsupported).  grow, for a key that leaves the batch out: nbytes_of()
+        is asked on every call and a held buffer that is smaller is replaced, so that a buffer ends up as large as the largest batch"""
+        nbytes = nbytes_of() if grow or key not in self._bufs else None
+        if nbytes == 0:
+            raise RuntimeError(unsupported)
         buf = self._bufs.pop(key, None)
-        if buf is None:
-            nbytes = nbytes_of()
-            if nbytes == 0:
-                raise RuntimeError(unsupported)
+        if buf is None or (grow and buf.numel() < nbytes):
             buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-            while len(self._bufs) >= 4:
-                self._bufs.pop(next(iter(self._bufs)))
+        while len(self._bufs) >= 4:
+            self._bufs.pop(next(iter(self._bufs)))
         self._bufs[key] = buf
         return buf
+
+
+def run_forward(net, call, key, nbytes_of, unsupported, forward, grow=False):
+    """Enqueues the launches first_launch..last_launch of the record `call` on the current stream of net.device: the scratch buffer of
+    (key, stream) out of net._scratch (sized by nbytes_of(), see ScratchCache.get), then the C entry point named `forward` on
+    net._weights and the record."""
+    with torch.cuda.device(net.device):
+        st = stream(net.device)
+        scratch = net._scratch.get(key + (st,), net.device, nbytes_of, unsupported, grow)
+        nat.check(getattr(nat.lib(), forward)(C.byref(net._weights), C.byref(call), scratch.data_ptr(), scratch.numel(), st), forward)

@@ -14,8 +14,6 @@
 #include "sgr_conv_mma.h"
 
 namespace sgr {
-int set_error(int code, const char* fmt, ...);
-
 namespace {
 
 constexpr int kMaxChannels = 1024;
@@ -32,10 +30,11 @@ __global__ void __launch_bounds__(kThreads) dpt_conv_kernel(const ConvArgs a) {
   __shared__ __attribute__((aligned(16))) half_t Xs[kBM * kRow];
   __shared__ __attribute__((aligned(16))) half_t Ws[BN * kRow];
   const SgrDptConv& c = a.c;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int m0 = blockIdx.x * kBM, n0 = blockIdx.y * BN;
+  const int tid = threadIdx.x, m0 = blockIdx.x * kBM, n0 = blockIdx.y * BN;
   const half_t* src = (const half_t*)c.src;
 
+  // This kernel keeps its own gather, not ConvWindow's: it addresses a tap as (first pixel of the image + y w + x) * stride, one
+  // 64-bit product, where the shared one adds the image to the product; the compiler's code for the two differs.
   int py[2], px[2];
   int64_t base[2];                                           // first pixel of the row's image
   bool pv[2];
@@ -59,18 +58,18 @@ __global__ void __launch_bounds__(kThreads) dpt_conv_kernel(const ConvArgs a) {
   // the ReLU in front of an RCU's conv1, four packed maxima per chunk on its way to LDS (the padding's zeros stay zeros)
   auto pre = [&](half8 v) { return relu_in ? __builtin_elementwise_max(v, half8{0, 0, 0, 0, 0, 0, 0, 0}) : v; };
   floatx4 acc[NT][2];
-  conv_mma_mainloop_pre<KS, BN>(Xs, Ws, (const half_t*)c.weight, n0, a.k_pad, c.cin, gather, pre, acc);
+  conv_mma_mainloop<KS, BN>(Xs, Ws, (const half_t*)c.weight, n0, a.k_pad, c.cin, gather, pre, acc);
 
-  // acc[t][j][r] is output channel n0 + 16 t + 4 (lane >> 4) + r of pixel m0 + 32 wave + 16 j + (lane & 15) of the batch
+  // acc[t][j] holds channels acc_channel(n0, t) .. + 3 of pixel acc_pixel(j) of the batch
   const half_t* res0 = (const half_t*)c.res0;
   const half_t* res1 = (const half_t*)c.res1;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int64_t m = m0 + wave * 32 + j * 16 + (lane & 15);
+    const int64_t m = acc_pixel(j);
     if (m >= a.M) continue;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      const int nb = n0 + t * 16 + (lane >> 4) * 4;
+      const int nb = acc_channel(n0, t);
       if (nb >= c.cout) continue;
       const bool full = nb + 4 <= c.cout;
       floatx4 v = acc[t][j];
@@ -250,13 +249,9 @@ int launch_conv(const SgrDptConv& c, hipStream_t stream) {
                      c.h, c.w, c.cin);
   if (c.cout < 1 || c.cout > kMaxChannels) return set_error(SGR_ERR_INVALID, "dpt_conv: cout %d outside 1..1024", c.cout);
   if (c.ksize != 1 && c.ksize != 3) return set_error(SGR_ERR_INVALID, "dpt_conv: kernel size %d is not 1 or 3", c.ksize);
-  if (c.src_stride < c.cin || c.src_stride % 8 || !aligned16(c.src))
-    return set_error(SGR_ERR_INVALID, "dpt_conv: src needs a 16-byte aligned base and a stride (%d) that is a multiple of 8 and >= %d", c.src_stride,
-                     c.cin);
-  const int k_pad = round_up(c.ksize * c.ksize * c.cin, kBK);
-  if (c.weight_elems < (int64_t)round_up(c.cout, 64) * k_pad || !aligned16(c.weight) || !aligned16(c.bias))
-    return set_error(SGR_ERR_INVALID, "dpt_conv: packed weights must be 16-byte aligned [%d][%d] fp16, got %lld elements", round_up(c.cout, 64),
-                     k_pad, (long long)c.weight_elems);
+  int k_pad;                                                 // (the rows are padded to whole tiles of 64)
+  if (int rc = check_conv_operands("dpt_conv", c.src, c.src_stride, c.cin, c.ksize, c.weight, c.weight_elems, round_up(c.cout, 64), c.bias, k_pad))
+    return rc;
   if (c.out_kind != SGR_UPDATE_OUT_CL_F16 && c.out_kind != SGR_UPDATE_OUT_CL_F32)
     return set_error(SGR_ERR_INVALID, "dpt_conv: the output is channels-last fp16 or fp32, got kind %d", c.out_kind);
   if (c.out_stride < c.cout || !aligned16(c.out) || (c.out_kind == SGR_UPDATE_OUT_CL_F16 && c.out_stride % 8))
@@ -281,7 +276,7 @@ int launch_conv(const SgrDptConv& c, hipStream_t stream) {
     dispatch_conv<16, 32, 64>(3, bn, [&](auto ks, auto bnc) {
       hipLaunchKernelGGL((dpt_conv_kernel<3, decltype(bnc)::value>), grid, block, 0, stream, a);
     });
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "dpt_conv launch failed");
+  return launched("dpt_conv");
 }
 
 int launch_up2(const half_t* src, int n, int h, int w, int C, int src_stride, half_t* dst, int dst_stride, hipStream_t stream) {
@@ -297,7 +292,7 @@ int launch_up2(const half_t* src, int n, int h, int w, int C, int src_stride, ha
   const int64_t blocks = (a.total + kThreads - 1) / kThreads;
   if (blocks > 0x7fffffff) return set_error(SGR_ERR_INVALID, "dpt_up2: the map is too large for one launch");
   hipLaunchKernelGGL(dpt_up2_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "dpt_up2 launch failed");
+  return launched("dpt_up2");
 }
 
 template <class Kernel>
@@ -311,7 +306,7 @@ int launch_resize(const char* what, Kernel kernel, const float* src, int planes,
   const int64_t blocks = (a.total + kThreads - 1) / kThreads;
   if (blocks > 0x7fffffff) return set_error(SGR_ERR_INVALID, "%s: the output is too large for one launch", what);
   hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kThreads), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "%s launch failed", what);
+  return launched(what);
 }
 
 bool sizes_ok(int n, int H, int W, int dim, int features) {
@@ -389,11 +384,8 @@ int sgr_dpt_forward(const SgrDptWeights* wt, const SgrDptCall* call, void* scrat
   if (scratch_bytes < s.bytes || !aligned16(scratch))
     return set_error(SGR_ERR_WORKSPACE, "dpt_forward: scratch of %zu bytes, need %zu (16-byte aligned)", scratch_bytes, s.bytes);
   hipStream_t stream = (hipStream_t)stream_;
-  int launch = -1, rc = SGR_OK, layer = 0;
-  auto on = [&]() {
-    ++launch;
-    return launch >= call->first_launch && launch <= call->last_launch;
-  };
+  int rc = SGR_OK, layer = 0;
+  LaunchRange on{call->first_launch, call->last_launch};
   // the next layer as one launch on an h x w map: out = relu?(conv(relu_in?(src)) + bias) + res0 + res1
   auto conv = [&](const half_t* src, int cin, int h, int w, int ks, int cout, int relu_in, int relu, const half_t* res0, const half_t* res1,
                   void* out, int out_kind = SGR_UPDATE_OUT_CL_F16) -> int {

@@ -13,8 +13,6 @@
 #include "sgr_conv_mma.h"
 
 namespace sgr {
-int set_error(int code, const char* fmt, ...);
-
 namespace {
 
 constexpr int kInPad = 8;                   // the 3 image channels padded to one 16-byte chunk
@@ -39,31 +37,28 @@ __global__ void __launch_bounds__(kThreads) enc_conv_kernel(const ConvArgs a) {
   const int img = blockIdx.z, m0 = blockIdx.x * kBM, n0 = blockIdx.y * BN;
   const half_t* src = (const half_t*)c.src + (int64_t)img * c.h * c.w * c.src_stride;
 
-  int iy[2], ix[2];
-  bool pv[2];
+  ConvWindow win;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int m = m0 + (tid >> 2) + 64 * i;
-    pv[i] = m < a.HWo;
-    const int mm = pv[i] ? m : 0, oy = mm / a.wo;
-    iy[i] = oy * c.stride;
-    ix[i] = (mm - oy * a.wo) * c.stride;
+    const bool pv = m < a.HWo;
+    const int mm = pv ? m : 0;
+    win.row(i, pv, mm, mm / a.wo, a.wo, c.stride, 0, 0);
   }
+  // the padding is a constant here and comes off the tap, not off the origin: the order of the sum this kernel was compiled with
   auto gather = [&](int i, bool tv, int ty, int tx, int ch) {
-    const int yy = iy[i] + ty - KS / 2, xx = ix[i] + tx - KS / 2;
-    half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (pv[i] && tv && (unsigned)yy < (unsigned)c.h && (unsigned)xx < (unsigned)c.w)
-      v = *(const half8*)(src + ((int64_t)yy * c.w + xx) * c.src_stride + ch);
-    return v;
+    return win.chunk(src, c.h, c.w, c.src_stride, i, tv, ty - KS / 2, tx - KS / 2, ch);
   };
   floatx4 acc[NT][2];
   conv_mma_mainloop<KS, BN>(Xs, Ws, (const half_t*)c.weight, n0, a.k_pad, c.cin, gather, acc);
 
-  // acc[t][j][r] is output channel n0 + 16 t + 4 (lane >> 4) + r of pixel m0 + 32 wave + 16 j + (lane & 15) of this image
+  // acc[t][j] holds channels acc_channel(n0, t) .. + 3 of pixel acc_pixel(j) of this image
   bool valid[2];
   int64_t gm[2];                                             // pixel index over the whole batch
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
+    // acc_pixel(j), spelled out: this kernel also indexes red by wave, and through the function the compiler folds that shared shift
+    // another way
     const int m = m0 + wave * 32 + j * 16 + (lane & 15);
     valid[j] = m < a.HWo;
     gm[j] = (int64_t)img * a.HWo + m;
@@ -77,7 +72,7 @@ __global__ void __launch_bounds__(kThreads) enc_conv_kernel(const ConvArgs a) {
     for (int j = 0; j < 2; ++j) {
       if (!valid[j]) continue;
 #pragma unroll
-      for (int t = 0; t < NT; ++t) *(floatx4*)&c.raw[gm[j] * c.cout + n0 + t * 16 + (lane >> 4) * 4] = acc[t][j];
+      for (int t = 0; t < NT; ++t) *(floatx4*)&c.raw[acc_channel(gm[j] * c.cout + n0, t)] = acc[t][j];
     }
     const float cnt = (float)min(kBM, a.HWo - m0);
 #pragma unroll
@@ -87,7 +82,7 @@ __global__ void __launch_bounds__(kThreads) enc_conv_kernel(const ConvArgs a) {
         float s = (valid[0] ? acc[t][0][r] : 0.f) + (valid[1] ? acc[t][1][r] : 0.f);
 #pragma unroll
         for (int d = 1; d < 16; d <<= 1) s += __shfl_xor(s, d);
-        if ((lane & 15) == 0) red[0][wave][t * 16 + (lane >> 4) * 4 + r] = s;
+        if ((lane & 15) == 0) red[0][wave][acc_channel(0, t) + r] = s;
       }
     __syncthreads();
     if (tid < BN) shift[tid] = (((red[0][0][tid] + red[0][1][tid]) + red[0][2][tid]) + red[0][3][tid]) / cnt;
@@ -109,7 +104,7 @@ __global__ void __launch_bounds__(kThreads) enc_conv_kernel(const ConvArgs a) {
     const int p = (int)(gm[j] - (int64_t)img * a.HWo);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      const int nb = n0 + t * 16 + (lane >> 4) * 4;
+      const int nb = acc_channel(n0, t);
       floatx4 v = acc[t][j] + *(const floatx4*)&c.bias[nb];
       if (c.act == SGR_ENCODER_ACT_SPLIT) {                  // cout = 256: tanh(net) | relu(inp), two NCHW fp16 tensors
         const bool lo = nb < 128;
@@ -212,13 +207,8 @@ int launch_conv(const SgrEncoderConv& c, hipStream_t stream) {
     return set_error(SGR_ERR_INVALID, "encoder_conv: cout %d is not 32, 64, 128 or 256", c.cout);
   if (c.ksize != 1 && c.ksize != 3 && c.ksize != 7) return set_error(SGR_ERR_INVALID, "encoder_conv: kernel size %d is not 1, 3 or 7", c.ksize);
   if (c.stride != 1 && c.stride != 2) return set_error(SGR_ERR_INVALID, "encoder_conv: stride %d is not 1 or 2", c.stride);
-  if (c.src_stride < c.cin || c.src_stride % 8 || !aligned16(c.src))
-    return set_error(SGR_ERR_INVALID, "encoder_conv: src needs a 16-byte aligned base and a stride (%d) that is a multiple of 8 and >= %d",
-                     c.src_stride, c.cin);
-  const int k_pad = round_up(c.ksize * c.ksize * c.cin, kBK);
-  if (c.weight_elems < (int64_t)c.cout * k_pad || !aligned16(c.weight) || !aligned16(c.bias))
-    return set_error(SGR_ERR_INVALID, "encoder_conv: packed weights must be 16-byte aligned [%d][%d] fp16, got %lld elements", c.cout, k_pad,
-                     (long long)c.weight_elems);
+  int k_pad;
+  if (int rc = check_conv_operands("encoder_conv", c.src, c.src_stride, c.cin, c.ksize, c.weight, c.weight_elems, c.cout, c.bias, k_pad)) return rc;
   if (c.act < SGR_ENCODER_ACT_NONE || c.act > SGR_ENCODER_ACT_SPLIT) return set_error(SGR_ERR_INVALID, "encoder_conv: unknown epilogue %d", c.act);
   if (c.residual && (c.residual_stride < c.cout || c.residual_stride % 8 || !aligned16(c.residual)))
     return set_error(SGR_ERR_INVALID, "encoder_conv: residual needs a 16-byte aligned base and a stride (%d) that is a multiple of 8 and >= %d",
@@ -253,7 +243,7 @@ int launch_conv(const SgrEncoderConv& c, hipStream_t stream) {
   dispatch_conv<32, 64>(c.ksize, bn, [&](auto ks, auto bnc) {
     hipLaunchKernelGGL((enc_conv_kernel<decltype(ks)::value, decltype(bnc)::value>), grid, block, 0, stream, a);
   });
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "encoder_conv launch failed");
+  return launched("encoder_conv");
 }
 
 // (the arguments were validated by launch_conv of the same record)
@@ -266,7 +256,7 @@ int launch_apply(const SgrEncoderConv& c, hipStream_t stream) {
   a.out_f32 = c.out_kind == SGR_UPDATE_OUT_CL_F32, a.out_stride = c.out_stride;
   const dim3 grid((unsigned)((a.HWo + kApplyPixels - 1) / kApplyPixels), (unsigned)c.n);
   hipLaunchKernelGGL(enc_apply_kernel, grid, dim3(kThreads), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "encoder_conv: apply launch failed");
+  return launched("encoder_conv: apply");
 }
 
 int launch_pack(const SgrUpdateTensor& src, int n, int H, int W, const float* mean, const float* std_, half_t* dst, hipStream_t stream) {
@@ -276,7 +266,7 @@ int launch_pack(const SgrUpdateTensor& src, int n, int H, int W, const float* me
   for (int i = 0; i < 3; ++i) a.mean[i] = mean ? mean[i] : 0.f, a.std_[i] = mean ? std_[i] : 1.f;
   a.HW = H * W, a.w = W;
   hipLaunchKernelGGL(enc_pack_kernel, dim3((unsigned)((a.HW + kThreads - 1) / kThreads), (unsigned)n), dim3(kThreads), 0, stream, a, dst);
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "encoder_pack launch failed");
+  return launched("encoder_pack");
 }
 
 // The maps of a call: level 0 the image, level 1 after the stem (32 channels), 2 after layer2 (64), 3 after layer3 (128).
@@ -357,11 +347,8 @@ int sgr_encoder_forward(const SgrEncoderWeights* wt, const SgrEncoderCall* call,
   if (scratch_bytes < s.bytes || !aligned16(scratch))
     return set_error(SGR_ERR_WORKSPACE, "encoder_forward: scratch of %zu bytes, need %zu (16-byte aligned)", scratch_bytes, s.bytes);
   hipStream_t stream = (hipStream_t)stream_;
-  int launch = -1, rc = SGR_OK;
-  auto on = [&]() {
-    ++launch;
-    return launch >= call->first_launch && launch <= call->last_launch;
-  };
+  int rc = SGR_OK;
+  LaunchRange on{call->first_launch, call->last_launch};
   // one convolution of the list: with a norm two launches (sums + statistics, apply), otherwise one
   auto conv = [&](int layer, const half_t* src, int cin, int lvl_in, int ks, int stride, int cout, int act, const half_t* res, void* out,
                   int out_kind, void* out2) -> int {

@@ -14,8 +14,6 @@
 #include "sgr_conv_mma.h"
 
 namespace sgr {
-int set_error(int code, const char* fmt, ...);
-
 namespace {
 
 constexpr int kInPad = 8;                                    // the 3 image channels padded to one 16-byte chunk
@@ -76,40 +74,31 @@ __global__ void __launch_bounds__(kThreads) lpips_conv_kernel(const ConvArgs a) 
   __shared__ __attribute__((aligned(16))) half_t Xs[kBM * kRow];
   __shared__ __attribute__((aligned(16))) half_t Ws[kBN * kRow];
   const SgrLpipsConv& c = a.c;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int m0 = blockIdx.x * kBM, n0 = blockIdx.y * kBN;
+  const int tid = threadIdx.x, m0 = blockIdx.x * kBM, n0 = blockIdx.y * kBN;
 
+  ConvWindow win;
   const half_t* src[2];                                      // the image of each of this thread's two pixel rows
-  int iy[2], ix[2];
-  bool pv[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int m = m0 + (tid >> 2) + 64 * i;
-    pv[i] = m < a.M;
-    const int mm = pv[i] ? m : 0, img = mm / a.HWo, p = mm - img * a.HWo, oy = p / a.wo;
+    const bool pv = m < a.M;
+    const int mm = pv ? m : 0, img = mm / a.HWo, p = mm - img * a.HWo, oy = p / a.wo;
     src[i] = (const half_t*)c.src + (int64_t)img * c.h * c.w * c.cin;
-    iy[i] = oy * c.stride - c.pad;
-    ix[i] = (p - oy * a.wo) * c.stride - c.pad;
+    win.row(i, pv, p, oy, a.wo, c.stride, c.pad, c.pad);
   }
-  auto gather = [&](int i, bool tv, int ty, int tx, int ch) {
-    const int yy = iy[i] + ty, xx = ix[i] + tx;
-    half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (pv[i] && tv && (unsigned)yy < (unsigned)c.h && (unsigned)xx < (unsigned)c.w)
-      v = *(const half8*)(src[i] + ((int64_t)yy * c.w + xx) * c.cin + ch);
-    return v;
-  };
+  auto gather = [&](int i, bool tv, int ty, int tx, int ch) { return win.chunk(src[i], c.h, c.w, c.cin, i, tv, ty, tx, ch); };
   floatx4 acc[NT][2];
   conv_mma_mainloop<KS, kBN>(Xs, Ws, (const half_t*)c.weight, n0, a.k_pad, c.cin, gather, acc);
 
-  // acc[t][j][r] is output channel n0 + 16 t + 4 (lane >> 4) + r of pixel m0 + 32 wave + 16 j + (lane & 15) of the batch
+  // acc[t][j] holds channels nb .. nb + 3 of pixel gm of the batch
   half_t* out = (half_t*)c.out;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int64_t gm = m0 + wave * 32 + j * 16 + (lane & 15);
+    const int64_t gm = acc_pixel(j);
     if (gm >= a.M) continue;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      const int nb = n0 + t * 16 + (lane >> 4) * 4;
+      const int nb = acc_channel(n0, t);
       const floatx4 v = acc[t][j] + *(const floatx4*)&c.bias[nb];
       half4 o;
 #pragma unroll
@@ -261,7 +250,7 @@ inline int dist_blocks(int P) { return (P + kDistPixels - 1) / kDistPixels; }
 int launch_pack(const PackTab& t, int H, int W, half_t* dst, hipStream_t stream) {
   const dim3 grid((unsigned)((t.HW + kThreads - 1) / kThreads), (unsigned)(2 * t.n));
   hipLaunchKernelGGL(lpips_pack_kernel, grid, dim3(kThreads), 0, stream, t, dst);
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "lpips_pack launch failed");
+  return launched("lpips_pack");
 }
 
 bool pack_sizes_ok(int n, int H, int W) { return n >= 1 && n <= SGR_LPIPS_MAX_PAIRS && map_ok(2 * n, H, W); }
@@ -317,7 +306,8 @@ int launch_conv(const SgrLpipsConv& c, hipStream_t stream) {
     return set_error(SGR_ERR_INVALID, "lpips_conv: bad sizes (n=%d h=%d w=%d cin=%d); n <= 65535, cin a multiple of 8 up to 1024", c.n, c.h, c.w, c.cin);
   if (c.cout < kBN || c.cout % kBN || c.cout > 1024) return set_error(SGR_ERR_INVALID, "lpips_conv: cout %d is not a multiple of 64 in 64..1024", c.cout);
   if (c.ksize != 11 && c.ksize != 5 && c.ksize != 3) return set_error(SGR_ERR_INVALID, "lpips_conv: kernel size %d is not 11, 5 or 3", c.ksize);
-  if (c.stride != 1 && c.stride != 4) return set_error(SGR_ERR_INVALID, "lpips_conv: stride %d is not 1 or 4", c.stride);
+  // (the trunk has strides 1 and 4; 2 is what the kernel shares with the encoder's and the ResNet's, and the tests hold the three to each other)
+  if (c.stride != 1 && c.stride != 2 && c.stride != 4) return set_error(SGR_ERR_INVALID, "lpips_conv: stride %d is not 1, 2 or 4", c.stride);
   if (c.pad < 0 || c.pad >= c.ksize) return set_error(SGR_ERR_INVALID, "lpips_conv: padding %d outside 0..ksize-1", c.pad);
   ConvArgs a;
   a.c = c;
@@ -333,7 +323,7 @@ int launch_conv(const SgrLpipsConv& c, hipStream_t stream) {
                      (long long)c.weight_elems);
   const dim3 grid((unsigned)tiles_of(a.M), (unsigned)(c.cout / kBN)), block(kThreads);
   dispatch_lpips_conv(c.ksize, [&](auto ks) { hipLaunchKernelGGL((lpips_conv_kernel<decltype(ks)::value>), grid, block, 0, stream, a); });
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "lpips_conv launch failed");
+  return launched("lpips_conv");
 }
 
 int launch_pool(const half_t* src, int n, int h, int w, int C, half_t* dst, hipStream_t stream) {
@@ -343,7 +333,7 @@ int launch_pool(const half_t* src, int n, int h, int w, int C, half_t* dst, hipS
   const int64_t blocks = (a.total + kThreads - 1) / kThreads;
   if (blocks > 0x7fffffff) return set_error(SGR_ERR_INVALID, "lpips_maxpool: the map is too large for one launch");
   hipLaunchKernelGGL(lpips_pool_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "lpips_maxpool launch failed");
+  return launched("lpips_maxpool");
 }
 
 int launch_dist(const half_t* maps, int n, int P, int C, const float* weight, float* partials, float* per_pixel, hipStream_t stream) {
@@ -357,7 +347,7 @@ int launch_dist(const half_t* maps, int n, int P, int C, const float* weight, fl
     case 384: hipLaunchKernelGGL(lpips_dist_kernel<6>, grid, block, 0, stream, a); break;
     default: return set_error(SGR_ERR_INVALID, "lpips_distance: %d channels; the taps have 64, 192, 256 or 384", C);
   }
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "lpips_distance launch failed");
+  return launched("lpips_distance");
 }
 
 // The sizes of a call and its maps.  Every launch reads one of two buffers and writes the other: the packed images, the pooled maps
@@ -452,11 +442,8 @@ int sgr_lpips_forward(const SgrLpipsWeights* wt, const SgrLpipsCall* call, void*
     if (!wt->conv[t].weight || !wt->conv[t].bias || !wt->lin[t] || !aligned16(wt->lin[t])) return set_error(SGR_ERR_INVALID, "lpips_forward: null or unaligned weights");
   if (!call->frames && (!call->img0 || !call->img1)) return set_error(SGR_ERR_INVALID, "lpips_forward: neither a frame table nor two images");
   hipStream_t stream = (hipStream_t)stream_;
-  int launch = -1, rc = SGR_OK;
-  auto on = [&]() {
-    ++launch;
-    return launch >= call->first_launch && launch <= call->last_launch;
-  };
+  int rc = SGR_OK;
+  LaunchRange on{call->first_launch, call->last_launch};
   if (on()) {
     rc = call->frames ? pack_frames(n, call->frames, H, W, wt->shift, wt->scale, s.xin, stream)
                       : pack_pairs(call->img0, call->img1, n, H, W, call->normalize, wt->shift, wt->scale, s.xin, stream);
@@ -481,7 +468,7 @@ int sgr_lpips_forward(const SgrLpipsWeights* wt, const SgrLpipsCall* call, void*
     for (int t = 0; t < kTaps; ++t) f.partials[t] = s.parts[t], f.pixels[t] = s.h[t] * s.w[t], f.blocks[t] = dist_blocks(f.pixels[t]);
     f.out = call->out, f.levels = call->levels;
     hipLaunchKernelGGL(lpips_final_kernel, dim3((unsigned)n), dim3(64), 0, stream, f);
-    if (hipGetLastError() != hipSuccess) return set_error(SGR_ERR_HIP, "lpips_forward: final launch failed");
+    if ((rc = launched("lpips_forward: final"))) return rc;
   }
   return SGR_OK;
 }

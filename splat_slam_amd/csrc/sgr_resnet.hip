@@ -16,8 +16,6 @@
 #include "sgr_conv_mma.h"
 
 namespace sgr {
-int set_error(int code, const char* fmt, ...);
-
 namespace {
 
 constexpr int kInPad = 8;                   // the 3 image channels padded to one 16-byte chunk
@@ -43,32 +41,24 @@ __global__ void __launch_bounds__(kThreads) resnet_conv_kernel(const ConvArgs a)
   const int img = blockIdx.z, m0 = blockIdx.x * kBM, n0 = blockIdx.y * BN;
   const half_t* src = (const half_t*)c.src + (int64_t)img * c.h * c.w * c.src_stride;
 
-  int iy[2], ix[2];
-  bool pv[2];
+  ConvWindow win;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int m = m0 + (tid >> 2) + 64 * i;
-    pv[i] = m < a.HWo;
-    const int mm = pv[i] ? m : 0, oy = mm / c.wo;
-    iy[i] = oy * c.stride - c.pad_top;
-    ix[i] = (mm - oy * c.wo) * c.stride - c.pad_left;
+    const bool pv = m < a.HWo;
+    const int mm = pv ? m : 0;
+    win.row(i, pv, mm, mm / c.wo, c.wo, c.stride, c.pad_top, c.pad_left);
   }
-  auto gather = [&](int i, bool tv, int ty, int tx, int ch) {
-    const int yy = iy[i] + ty, xx = ix[i] + tx;
-    half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (pv[i] && tv && (unsigned)yy < (unsigned)c.h && (unsigned)xx < (unsigned)c.w)
-      v = *(const half8*)(src + ((int64_t)yy * c.w + xx) * c.src_stride + ch);
-    return v;
-  };
+  auto gather = [&](int i, bool tv, int ty, int tx, int ch) { return win.chunk(src, c.h, c.w, c.src_stride, i, tv, ty, tx, ch); };
   floatx4 acc[NT][2];
   conv_mma_mainloop<KS, BN>(Xs, Ws, (const half_t*)c.weight, n0, a.k_pad, c.cin, gather, acc);
 
-  // acc[t][j][r] is output channel n0 + 16 t + 4 (lane >> 4) + r of pixel m0 + 32 wave + 16 j + (lane & 15) of this image
+  // acc[t][j] holds channels acc_channel(n0, t) .. + 3 of pixel acc_pixel(j) of this image
   bool valid[2];
   int64_t gm[2];                                             // pixel index over the whole batch
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int m = m0 + wave * 32 + j * 16 + (lane & 15);
+    const int m = acc_pixel(j);
     valid[j] = m < a.HWo;
     gm[j] = (int64_t)img * a.HWo + m;
   }
@@ -81,7 +71,7 @@ __global__ void __launch_bounds__(kThreads) resnet_conv_kernel(const ConvArgs a)
     for (int j = 0; j < 2; ++j) {
       if (!valid[j]) continue;
 #pragma unroll
-      for (int t = 0; t < NT; ++t) *(floatx4*)&c.raw[gm[j] * c.cout + n0 + t * 16 + (lane >> 4) * 4] = acc[t][j];
+      for (int t = 0; t < NT; ++t) *(floatx4*)&c.raw[acc_channel(gm[j] * c.cout + n0, t)] = acc[t][j];
     }
     const int cmask = (1 << a.cshift) - 1;
     if (wave == 0 && (lane & 15) == 0) {
@@ -89,7 +79,7 @@ __global__ void __launch_bounds__(kThreads) resnet_conv_kernel(const ConvArgs a)
       for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int n = t * 16 + (lane >> 4) * 4 + r;
+          const int n = acc_channel(0, t) + r;
           if ((n & cmask) == 0) shift[n >> a.cshift] = acc[t][0][r];
         }
     }
@@ -115,7 +105,7 @@ __global__ void __launch_bounds__(kThreads) resnet_conv_kernel(const ConvArgs a)
     const int p = (int)(gm[j] - (int64_t)img * a.HWo);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      const int nb = n0 + t * 16 + (lane >> 4) * 4;
+      const int nb = acc_channel(n0, t);
       floatx4 v = acc[t][j];
       if (c.bias) v += *(const floatx4*)&c.bias[nb];
       if (c.act == SGR_RESNET_ACT_RELU)
@@ -259,13 +249,8 @@ int launch_conv(const SgrResnetConv& c, hipStream_t stream) {
   if (!out_ok(c.h, c.pad_top, c.ho) || !out_ok(c.w, c.pad_left, c.wo) || !map_ok(c.n, c.ho, c.wo))
     return set_error(SGR_ERR_INVALID, "resnet_conv: output %d x %d does not follow from a %d x %d map, kernel %d, stride %d, padding (%d, %d)",
                      c.ho, c.wo, c.h, c.w, c.ksize, c.stride, c.pad_top, c.pad_left);
-  if (c.src_stride < c.cin || c.src_stride % 8 || !aligned16(c.src))
-    return set_error(SGR_ERR_INVALID, "resnet_conv: src needs a 16-byte aligned base and a stride (%d) that is a multiple of 8 and >= %d",
-                     c.src_stride, c.cin);
-  const int k_pad = round_up(c.ksize * c.ksize * c.cin, kBK);
-  if (c.weight_elems < (int64_t)c.cout * k_pad || !aligned16(c.weight) || !aligned16(c.bias))
-    return set_error(SGR_ERR_INVALID, "resnet_conv: packed weights must be 16-byte aligned [%d][%d] fp16, got %lld elements", c.cout, k_pad,
-                     (long long)c.weight_elems);
+  int k_pad;
+  if (int rc = check_conv_operands("resnet_conv", c.src, c.src_stride, c.cin, c.ksize, c.weight, c.weight_elems, c.cout, c.bias, k_pad)) return rc;
   ConvArgs a;
   a.c = c;
   a.HWo = c.ho * c.wo;
@@ -298,7 +283,7 @@ int launch_conv(const SgrResnetConv& c, hipStream_t stream) {
   dispatch_conv<16, 32, 64>(c.ksize, bn, [&](auto ks, auto bnc) {
     hipLaunchKernelGGL((resnet_conv_kernel<decltype(ks)::value, decltype(bnc)::value>), grid, block, 0, stream, a);
   });
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "resnet_conv launch failed");
+  return launched("resnet_conv");
 }
 
 // pixels of one workgroup of the norm launch: about 16384 elements, and at least as many pixels as the image has tiles, so that the
@@ -330,7 +315,7 @@ int launch_norm(const SgrResnetNorm& g, hipStream_t stream) {
   a.res_stride = g.residual_stride, a.out_stride = g.out_stride, a.pixels = norm_pixels(g.hw, g.cout);
   const dim3 grid((unsigned)((g.hw + a.pixels - 1) / a.pixels), (unsigned)g.n);
   hipLaunchKernelGGL(resnet_norm_kernel, grid, dim3(kThreads), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "resnet_groupnorm launch failed");
+  return launched("resnet_groupnorm");
 }
 
 int launch_pool(const half_t* src, int n, int h, int w, int C, half_t* dst, hipStream_t stream) {
@@ -341,7 +326,7 @@ int launch_pool(const half_t* src, int n, int h, int w, int C, half_t* dst, hipS
   const int64_t blocks = (a.total + kThreads - 1) / kThreads;
   if (blocks > 0x7fffffff) return set_error(SGR_ERR_INVALID, "resnet_maxpool: the map is too large for one launch");
   hipLaunchKernelGGL(resnet_pool_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "resnet_maxpool launch failed");
+  return launched("resnet_maxpool");
 }
 
 bool widths_ok(int stem, const int* chs) {
@@ -414,7 +399,7 @@ int sgr_resnet_stats(const float* raw, int32_t n, int32_t hw, int32_t cout, int3
   StatsArgs a;
   a.raw = raw, a.stats = stats, a.HW = hw, a.tiles = tiles_of(hw), a.C = cout, a.G = groups, a.cshift = cshift;
   hipLaunchKernelGGL(resnet_stats_kernel, dim3((unsigned)a.tiles, (unsigned)n), dim3(kThreads), 0, (hipStream_t)stream, a);
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "resnet_stats launch failed");
+  return launched("resnet_stats");
 }
 
 int sgr_resnet_groupnorm(const SgrResnetNorm* norm, void* stream) {
@@ -452,11 +437,8 @@ int sgr_resnet_forward(const SgrResnetWeights* wt, const SgrResnetCall* call, vo
   if (scratch_bytes < s.bytes || !aligned16(scratch))
     return set_error(SGR_ERR_WORKSPACE, "resnet_forward: scratch of %zu bytes, need %zu (16-byte aligned)", scratch_bytes, s.bytes);
   hipStream_t stream = (hipStream_t)stream_;
-  int launch = -1, rc = SGR_OK;
-  auto on = [&]() {
-    ++launch;
-    return launch >= call->first_launch && launch <= call->last_launch;
-  };
+  int rc = SGR_OK;
+  LaunchRange on{call->first_launch, call->last_launch};
   // one convolution with TF "same" padding and its norm: two launches
   auto conv = [&](int layer, const half_t* src, int cin, int h, int w, int ks, int stride, int cout, int relu, const half_t* res,
                   half_t* out) -> int {

@@ -11,8 +11,6 @@
 #include "sgr_conv_mma.h"
 
 namespace sgr {
-int set_error(int code, const char* fmt, ...);
-
 namespace {
 
 constexpr int kNPad = 64;                   // packed weights have their rows padded to a multiple of this
@@ -37,8 +35,7 @@ __global__ void __launch_bounds__(kThreads) conv_kernel(const ConvArgs a) {
   __shared__ __attribute__((aligned(16))) half_t Xs[kBM * kRow];
   __shared__ __attribute__((aligned(16))) half_t Ws[BN * kRow];
   const SgrUpdateConv& c = a.c;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int m0 = blockIdx.x * kBM, n0 = blockIdx.y * BN;
+  const int tid = threadIdx.x, m0 = blockIdx.x * kBM, n0 = blockIdx.y * BN;
   const half_t* src0 = (const half_t*)c.src0;
   const half_t* src1 = (const half_t*)c.src1;
 
@@ -66,19 +63,19 @@ __global__ void __launch_bounds__(kThreads) conv_kernel(const ConvArgs a) {
   floatx4 acc[NT][2];
   conv_mma_mainloop<KS, BN>(Xs, Ws, (const half_t*)c.weight, n0, a.k_pad, c.cin, gather, acc);
 
-  // epilogue: acc[t][j][r] is output channel n0 + 16 t + 4 (lane >> 4) + r of pixel m0 + 32 wave + 16 j + (lane & 15)
+  // epilogue: acc[t][j][r] is channel acc_channel(n0, t) + r of pixel acc_pixel(j)
   const half_t* aux0 = (const half_t*)c.aux0;
   const half_t* aux1 = (const half_t*)c.aux1;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int m = m0 + wave * 32 + j * 16 + (lane & 15);
+    const int m = acc_pixel(j);
     if (m >= a.M) continue;
     const int e = m / a.HW, p = m - e * a.HW;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int n = n0 + t * 16 + (lane >> 4) * 4 + r;
+        const int n = acc_channel(n0, t) + r;
         if (n >= c.cout) continue;
         float v = acc[t][j][r] + c.bias[n];
         if (c.eadd) v += c.eadd[(int64_t)e * c.eadd_stride + n];
@@ -236,14 +233,14 @@ int launch_conv(const SgrUpdateConv& c, hipStream_t stream) {
   dispatch_conv<16, 64>(c.ksize, narrow ? 16 : 64, [&](auto ks, auto bn) {
     hipLaunchKernelGGL((conv_kernel<decltype(ks)::value, decltype(bn)::value>), grid, block, 0, stream, a);
   });
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "update_conv launch failed");
+  return launched("update_conv");
 }
 
 int launch_pack(const SgrUpdateTensor& src, int E, int C, int h, int w, half_t* dst, int dst_stride, int c_pad, hipStream_t stream) {
   const int64_t M = (int64_t)E * h * w, total = M * (c_pad / 8), nblocks = (total + kThreads - 1) / kThreads;
   if (nblocks > 0x7fffffff) return set_error(SGR_ERR_CAPACITY, "update_pack: too many elements");
   hipLaunchKernelGGL(pack_kernel, dim3((unsigned)nblocks), dim3(kThreads), 0, stream, src, (int)M, h * w, w, C, dst, dst_stride, c_pad / 8);
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "update_pack launch failed");
+  return launched("update_pack");
 }
 
 // Scratch of one call, in halfs per pixel of the E edges unless noted.  hid2 holds z | r*net during the GRU and the two hidden maps
@@ -316,11 +313,7 @@ int sgr_update_forward(const SgrUpdateWeights* wt, const SgrUpdateCall* call, vo
   if (scratch_bytes < s.bytes || !aligned16(scratch))
     return set_error(SGR_ERR_WORKSPACE, "update_forward: scratch of %zu bytes, need %zu (16-byte aligned)", scratch_bytes, s.bytes);
   hipStream_t stream = (hipStream_t)stream_;
-  int launch = -1;
-  auto on = [&]() {
-    ++launch;
-    return launch >= call->first_launch && launch <= call->last_launch;
-  };
+  LaunchRange on{call->first_launch, call->last_launch};
   auto conv = [&](int layer, const half_t* src0, int stride0, const half_t* src1, int stride1, int split, int cin, int ks, int edges, int cout,
                   int act, const float* eadd, const half_t* aux0, int aux0_stride, const half_t* aux1, void* out, int out_kind, int out_stride,
                   void* out2, int out2_stride) {
@@ -359,7 +352,7 @@ int sgr_update_forward(const SgrUpdateWeights* wt, const SgrUpdateCall* call, vo
     return rc;
   if (on()) {
     hipLaunchKernelGGL(glo_kernel, dim3(E), dim3(kThreads), 0, stream, (const half_t*)s.tmp, h * w, wt->glo_weight, wt->glo_bias, s.glo);
-    if (hipGetLastError() != hipSuccess) return set_error(SGR_ERR_HIP, "update_forward: glo launch failed");
+    if ((rc = launched("update_forward: glo"))) return rc;
   }
   if (on() && (rc = conv(5, s.cat, kCat, nullptr, 0, 0, kCat, 3, E, 2 * kHidden, SGR_UPDATE_ACT_ZR, s.glo, s.cat, kCat, nullptr, z, CL, kHidden, rnet,
                          kHidden)))
@@ -383,7 +376,7 @@ int sgr_update_forward(const SgrUpdateWeights* wt, const SgrUpdateCall* call, vo
   if (on()) {
     const int64_t nblocks = (MK * 16 + kThreads - 1) / kThreads;
     hipLaunchKernelGGL(segmean_kernel, dim3((unsigned)nblocks), dim3(kThreads), 0, stream, (const half_t*)s.tmp, call->ix, E, K, h * w, s.agg);
-    if (hipGetLastError() != hipSuccess) return set_error(SGR_ERR_HIP, "update_forward: segmented mean launch failed");
+    if ((rc = launched("update_forward: segmented mean"))) return rc;
   }
   if (on() && (rc = conv(11, s.agg, kHidden, nullptr, 0, 0, kHidden, 3, K, kHidden, RELU, nullptr, nullptr, 0, nullptr, s.agg2, CL, kHidden, nullptr, 0)))
     return rc;

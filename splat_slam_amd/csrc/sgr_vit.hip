@@ -13,8 +13,6 @@
 #include "sgr_conv_mma.h"                   // the vector types and the host helpers; the GEMM here has its own tile
 
 namespace sgr {
-int set_error(int code, const char* fmt, ...);
-
 namespace {
 
 typedef short short4v __attribute__((__vector_size__(8)));
@@ -318,7 +316,7 @@ int launch_layernorm(const float* x, const float* gamma, const float* beta, int6
     return set_error(SGR_ERR_INVALID, "vit_layernorm: bad sizes (M=%lld D=%d); D is a multiple of 64 up to %d", (long long)M, D, 64 * kMaxHeads);
   if (!aligned16(out)) return set_error(SGR_ERR_INVALID, "vit_layernorm: out must be 16-byte aligned");
   hipLaunchKernelGGL(layernorm_kernel, dim3((unsigned)((M + 3) / 4)), dim3(kThreads), 0, stream, x, gamma, beta, M, D, out);
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "vit_layernorm launch failed");
+  return launched("vit_layernorm");
 }
 
 int launch_gemm(const SgrVitGemm& g, hipStream_t stream) {
@@ -346,7 +344,7 @@ int launch_gemm(const SgrVitGemm& g, hipStream_t stream) {
     hipLaunchKernelGGL(gemm_kernel<4>, grid, block, 0, stream, g);
   else
     hipLaunchKernelGGL(gemm_kernel<2>, grid, block, 0, stream, g);
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "vit_gemm launch failed");
+  return launched("vit_gemm");
 }
 
 int launch_attention(const half_t* qkv, int B, int T, int heads, half_t* out, hipStream_t stream) {
@@ -356,7 +354,7 @@ int launch_attention(const half_t* qkv, int B, int T, int heads, half_t* out, hi
   if (!aligned16(qkv) || !aligned16(out)) return set_error(SGR_ERR_INVALID, "vit_attention: qkv and out must be 16-byte aligned");
   hipLaunchKernelGGL(attention_kernel, dim3((unsigned)((T + kQB - 1) / kQB), (unsigned)heads, (unsigned)B), dim3(kThreads), 0, stream, qkv, T,
                      heads, out);
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "vit_attention launch failed");
+  return launched("vit_attention");
 }
 
 // Scratch of one call.  xn: a normalised row; hid: the MLP's hidden rows; rv: the class-token half of the two readouts.
@@ -423,11 +421,7 @@ int sgr_vit_forward(const SgrVitWeights* wt, const SgrVitCall* call, void* scrat
   if (scratch_bytes < s.bytes || !aligned16(scratch))
     return set_error(SGR_ERR_WORKSPACE, "vit_forward: scratch of %zu bytes, need %zu (16-byte aligned)", scratch_bytes, s.bytes);
   hipStream_t stream = (hipStream_t)stream_;
-  int launch = -1;
-  auto on = [&]() {
-    ++launch;
-    return launch >= call->first_launch && launch <= call->last_launch;
-  };
+  LaunchRange on{call->first_launch, call->last_launch};
   auto gemm = [&](const void* a, int64_t lda, const void* w, int64_t ldw, const float* bias, int m, int n, int k, int epi, void* out, int64_t ldo,
                   void* tap, const float* aux) {
     SgrVitGemm g = {};
@@ -438,7 +432,7 @@ int sgr_vit_forward(const SgrVitWeights* wt, const SgrVitCall* call, void* scrat
   int rc = SGR_OK;
   if (on()) {
     hipLaunchKernelGGL(cls_kernel, dim3((unsigned)((B * D + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, call->pos, B, T, D, s.stream);
-    if (hipGetLastError() != hipSuccess) return set_error(SGR_ERR_HIP, "vit_forward: class-token launch failed");
+    if ((rc = launched("vit_forward: class-token"))) return rc;
     if ((rc = gemm(call->patches, wt->cin, wt->embed_w, wt->cin, wt->embed_b, B * (T - 1), D, wt->cin, SGR_VIT_EPI_EMBED, s.stream, D, nullptr,
                    call->pos)))
       return rc;

@@ -25,7 +25,8 @@ from fractions import Fraction
 import torch
 
 from splat_slam_amd import _native as nat
-from splat_slam_amd._nn_common import ScratchCache, pack_bias, pack_weight, round_up, stream, tensor_desc
+from splat_slam_amd._nn_common import (F16_F32, ScratchCache, gpu_tensor, network_device, pack_bias, pack_weight, round_up, run_forward, stream,
+                                       tensor_desc)
 
 __all__ = ["DPTDecoder", "LAUNCH_NAMES", "LAYER_NAMES", "pack_nchw", "conv_cl_f16", "up2_cl_f16", "resize_in", "resize_out", "aa_taps",
            "cubic_taps", "up2_taps"]
@@ -49,17 +50,9 @@ def LAYER_NAMES(cfg=None):
                  if not n.startswith("pack") and not n.endswith("up2"))
 
 
-def _gpu(what, name, t, dtypes):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{what} (MI355X build): {name} must be a GPU tensor; there is no CPU path")
-    if t.dtype not in dtypes:
-        raise RuntimeError(f"{what}: {name} must be one of {dtypes}, got {t.dtype}")
-    return t
-
-
 def _cl(what, name, t):
     """the row stride of a channels-last map [B,h,w,C]"""
-    _gpu(what, name, t, (torch.float16,))
+    gpu_tensor(what, name, t, (torch.float16,))
     if t.dim() != 4 or min(t.shape) < 1:
         raise RuntimeError(f"{what}: {name} must be a non-empty [B,h,w,C], got {tuple(t.shape)}")
     B, h, w, ch = t.shape
@@ -75,7 +68,7 @@ def _cl(what, name, t):
 # ---- the single kernels ----------------------------------------------------------------------------------------------------------------
 def pack_nchw(x):
     """[B,C,h,w] fp16 or fp32, any strides -> fp16 [B, h * w, C], C a multiple of 8 (sgr_update_pack)"""
-    _gpu("dpt_decoder.pack_nchw", "x", x, (torch.float16, torch.float32))
+    gpu_tensor("dpt_decoder.pack_nchw", "x", x, F16_F32)
     B, ch, h, w = x.shape
     if ch % 8:
         raise RuntimeError(f"dpt_decoder.pack_nchw: {ch} channels are no multiple of 8")
@@ -92,9 +85,9 @@ def conv_cl_f16(x, w, b=None, relu_in=False, relu=False, res0=None, res1=None, o
     [B,h,w,cout].  The result is [B,h,w,cout], fp16 or fp32."""
     what = "dpt_decoder.conv_cl_f16"
     sx = _cl(what, "x", x)
-    _gpu(what, "w", w, (torch.float16, torch.float32))
+    gpu_tensor(what, "w", w, F16_F32)
     if b is not None:
-        _gpu(what, "b", b, (torch.float16, torch.float32))
+        gpu_tensor(what, "b", b, F16_F32)
     if w.dim() != 4 or w.shape[1] != x.shape[3] or w.shape[2] != w.shape[3]:
         raise RuntimeError(f"{what}: x [B,h,w,cin] and w [cout,cin,k,k], got {tuple(x.shape)} and {tuple(w.shape)}")
     if out_dtype not in (torch.float16, torch.float32):
@@ -133,7 +126,7 @@ def up2_cl_f16(x):
 
 
 def _planes(what, t, size):
-    _gpu(what, "the input", t, (torch.float32,))
+    gpu_tensor(what, "the input", t, (torch.float32,))
     if t.dim() < 2 or min(t.shape) < 1 or len(size) != 2 or min(size) < 1:
         raise RuntimeError(f"{what}: a non-empty [..., H, W] and a size (h, w), got {tuple(t.shape)} and {tuple(size)}")
     return t.contiguous(), int(t.numel() // (t.shape[-1] * t.shape[-2]))
@@ -196,11 +189,7 @@ class DPTDecoder:
         if D % 16 or f % 16 or D > 1024 or f > 1024 or any(c % 8 or c > 1024 for c in cfg.stage_chs[:2]):
             raise ValueError(f"dpt_decoder: dim and features are multiples of 16, the stage widths multiples of 8, all up to 1024; got {cfg}")
         self.cfg = cfg
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("dpt_decoder (MI355X build): the decoder lives on a GPU; there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = network_device(device, "dpt_decoder", "decoder")
         dev = self.device
         self._keep = []
         w = self._weights = nat.SgrDptWeights()
@@ -224,7 +213,7 @@ class DPTDecoder:
         if H < 32 or H % 32 or W < 32 or W % 32:
             raise ValueError(f"dpt_decoder: H and W must be positive multiples of 32, got {H} x {W}")
         for name, t in (("tap3", tap3), ("tap4", tap4), ("l1", l1), ("l2", l2)):
-            _gpu(what, name, t, (torch.float16,))
+            gpu_tensor(what, name, t, (torch.float16,))
             if t.device != self.device:
                 raise RuntimeError(f"dpt_decoder: {name} is on {t.device}, the decoder on {self.device}")
         B = tap3.shape[0]
@@ -243,14 +232,9 @@ class DPTDecoder:
 
     def _run(self, call):
         """enqueues the launches first_launch..last_launch of the record on the current stream"""
-        with torch.cuda.device(self.device):
-            st = stream(self.device)
-            n, H, W = call.n, call.H, call.W
-            scratch = self._scratch.get((n, H, W, st), self.device,
-                                        lambda: nat.lib().sgr_dpt_scratch_bytes(n, H, W, self.cfg.dim, self.cfg.features),
-                                        f"dpt_decoder: unsupported sizes (n={n} H={H} W={W})")
-            nat.check(nat.lib().sgr_dpt_forward(C.byref(self._weights), C.byref(call), scratch.data_ptr(), scratch.numel(), st),
-                      "sgr_dpt_forward")
+        n, H, W = call.n, call.H, call.W
+        run_forward(self, call, (n, H, W), lambda: nat.lib().sgr_dpt_scratch_bytes(n, H, W, self.cfg.dim, self.cfg.features),
+                    f"dpt_decoder: unsupported sizes (n={n} H={H} W={W})", "sgr_dpt_forward")
 
     def __call__(self, tap3, tap4, l1, l2, H, W):
         call, depth = self._prepare(tap3, tap4, l1, l2, H, W)

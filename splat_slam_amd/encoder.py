@@ -24,7 +24,8 @@ import numpy as np
 import torch
 
 from splat_slam_amd import _native as nat
-from splat_slam_amd._nn_common import ScratchCache, hash_uniform, pack_bias, pack_weight, round_up, stream, tensor_desc
+from splat_slam_amd._nn_common import (F16_F32, ScratchCache, gpu_tensor, hash_uniform, network_device, pack_bias, pack_weight, round_up,
+                                       run_forward, stream, tensor_desc)
 
 __all__ = ["Encoder", "synthetic_encoder_state_dict", "normalize_encoder_state_dict", "conv2d_f16", "ENCODER_LAYERS", "LAYER_SHAPES",
            "LAUNCH_NAMES", "OUT_DIM", "NORM"]
@@ -121,13 +122,6 @@ def _out_size(v, stride):
     return (v - 1) // stride + 1
 
 
-def _check_tensor(what, name, t):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{what} (MI355X build): {name} must be a GPU tensor; there is no CPU path")
-    if t.dtype not in (torch.float16, torch.float32):
-        raise RuntimeError(f"{what}: {name} must be fp16 or fp32, got {t.dtype}")
-
-
 def _three(what, name, v):
     v = [float(x) for x in (v.reshape(-1).tolist() if isinstance(v, torch.Tensor) else v)]
     if len(v) != 3:
@@ -143,7 +137,7 @@ def conv2d_f16(x, w, b=None, stride=1, norm=None, act="none", residual=None, out
     result [B,cout,ho,wo] is out_dtype (fp16 or fp32), ho = (h - 1) // stride + 1."""
     what = "encoder.conv2d_f16"
     for name, t in (("x", x), ("w", w)) + ((("b", b),) if b is not None else ()) + ((("residual", residual),) if residual is not None else ()):
-        _check_tensor(what, name, t)
+        gpu_tensor(what, name, t, F16_F32, "fp16 or fp32")
     if act not in nat.SGR_ENCODER_ACTS:
         raise RuntimeError(f"{what}: act must be one of {sorted(nat.SGR_ENCODER_ACTS)}, got {act!r}")
     if norm not in (None, "none", "instance"):
@@ -212,11 +206,7 @@ class Encoder:
         self.which = _which(which)
         sd = normalize_encoder_state_dict(sd, which)
         self.out_dim, self.norm = OUT_DIM[which], NORM[which]
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("encoder (MI355X build): the encoder lives on a GPU; there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = network_device(device, "encoder", "encoder")
         self._keep = []
         self._weights = nat.SgrEncoderWeights()
         self._weights.out_dim = self.out_dim
@@ -242,7 +232,7 @@ class Encoder:
     def _prepare(self, images, mean, std, split):
         """checks the arguments, allocates the outputs and fills the call record: (record, outputs)"""
         what = f"encoder {self.which}"
-        _check_tensor(what, "images", images)
+        gpu_tensor(what, "images", images, F16_F32, "fp16 or fp32")
         if images.device != self.device:
             raise RuntimeError(f"{what}: images is on {images.device}, the encoder on {self.device}")
         if images.dim() != 5 or images.shape[2] != 3:
@@ -279,14 +269,9 @@ class Encoder:
 
     def _run(self, call):
         """enqueues the launches first_launch..last_launch of the record on the current stream"""
-        with torch.cuda.device(self.device):
-            st = stream(self.device)
-            n, H, W = call.n, call.H, call.W
-            scratch = self._scratch.get((n, H, W, st), self.device,
-                                        lambda: nat.lib().sgr_encoder_scratch_bytes(n, H, W, self.out_dim, self._weights.norm),
-                                        f"encoder {self.which}: unsupported sizes (n={n} H={H} W={W})")
-            nat.check(nat.lib().sgr_encoder_forward(C.byref(self._weights), C.byref(call), scratch.data_ptr(), scratch.numel(), st),
-                      "sgr_encoder_forward")
+        n, H, W = call.n, call.H, call.W
+        run_forward(self, call, (n, H, W), lambda: nat.lib().sgr_encoder_scratch_bytes(n, H, W, self.out_dim, self._weights.norm),
+                    f"encoder {self.which}: unsupported sizes (n={n} H={H} W={W})", "sgr_encoder_forward")
 
     def __call__(self, images, mean=None, std=None):
         call, out = self._prepare(images, mean, std, False)

@@ -28,7 +28,8 @@ import numpy as np
 import torch
 
 from splat_slam_amd import _native as nat
-from splat_slam_amd._nn_common import hash_uniform, pack_bias, pack_weight, round_up, stream
+from splat_slam_amd._nn_common import (F16_F32, ScratchCache, gpu_tensor, hash_uniform, network_device, pack_bias, pack_weight, round_up,
+                                       run_forward, stream)
 
 __all__ = ["LPIPS", "LAUNCH_NAMES", "CHANNELS", "CONV_SHAPES", "SHIFT", "SCALE", "CHUNK", "normalize_state_dict", "parts_state_dict",
            "synthetic_state_dict", "prepare", "tap_sizes", "pack_conv", "pack_pairs", "pack_frames", "conv_relu_f16", "max_pool_f16",
@@ -161,14 +162,6 @@ def pack_conv(w16):
 
 
 # ---- the single kernels ----------------------------------------------------------------------------------------------------------------
-def _gpu(what, name, t, dtypes):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{what} (MI355X build): {name} must be a GPU tensor; there is no CPU path")
-    if t.dtype not in dtypes:
-        raise RuntimeError(f"{what}: {name} must be one of {dtypes}, got {t.dtype}")
-    return t
-
-
 def _f3(v):
     return (C.c_float * 3)(*[float(x) for x in v])
 
@@ -176,7 +169,7 @@ def _f3(v):
 def pack_pairs(img0, img1, normalize=True, shift=SHIFT, scale=SCALE):
     """sgr_lpips_pack_pairs: two fp32 [n,3,H,W] (n <= 16) -> fp16 [2n,H,W,8]"""
     for name, t in (("img0", img0), ("img1", img1)):
-        _gpu("lpips.pack_pairs", name, t, (torch.float32,))
+        gpu_tensor("lpips.pack_pairs", name, t, (torch.float32,))
     n, _, H, W = img0.shape
     a, b = img0.contiguous(), img1.contiguous()
     out = torch.empty((2 * n, H, W, 8), dtype=torch.float16, device=img0.device)
@@ -207,7 +200,7 @@ def conv_relu_f16(x, w, bias, stride, pad):
     """relu(conv2d(x, w, bias, stride, pad)) on sgr_lpips_conv: x [B,cin,h,w], w [cout,cin,k,k] (k 11, 5 or 3; cout a multiple of 64) and
     bias are rounded to fp16, the sums are fp32; the result is fp16 [B,cout,ho,wo], a channels-last strided view"""
     for name, t in (("x", x), ("w", w), ("bias", bias)):
-        _gpu("lpips.conv_relu_f16", name, t, (torch.float16, torch.float32))
+        gpu_tensor("lpips.conv_relu_f16", name, t, F16_F32)
     B, cin, h, wd = x.shape
     cout, k = w.shape[0], w.shape[2]
     ho, wo = (h + 2 * pad - k) // stride + 1, (wd + 2 * pad - k) // stride + 1
@@ -229,7 +222,7 @@ def conv_relu_f16(x, w, bias, stride, pad):
 def max_pool_f16(x):
     """max_pool2d(x, 3, 2) without padding on sgr_lpips_maxpool: fp16 [B,C,h,w] (C a multiple of 8) -> fp16 [B,C,(h-3)//2+1,(w-3)//2+1], a
     channels-last strided view"""
-    _gpu("lpips.max_pool_f16", "x", x, (torch.float16,))
+    gpu_tensor("lpips.max_pool_f16", "x", x, (torch.float16,))
     B, ch, h, w = x.shape
     if min(h, w) < 3:
         raise RuntimeError(f"lpips.max_pool_f16: h and w >= 3, got {h} x {w}")
@@ -244,8 +237,8 @@ def distance(f0, f1, weight):
     """one tap on sgr_lpips_distance: f0, f1 fp16 [n,P,C] channels-last, weight fp32 [C] -> (partials fp32 [n, ceil(P / 128)], the sums of
     d_p over each workgroup's pixels; per_pixel fp32 [n,P]).  The tap's distance is partials.double().sum(1) / P."""
     for name, t in (("f0", f0), ("f1", f1)):
-        _gpu("lpips.distance", name, t, (torch.float16,))
-    _gpu("lpips.distance", "weight", weight, (torch.float32,))
+        gpu_tensor("lpips.distance", name, t, (torch.float16,))
+    gpu_tensor("lpips.distance", "weight", weight, (torch.float32,))
     n, P, ch = f0.shape
     maps = torch.cat([f0, f1]).contiguous()
     w = weight.contiguous()
@@ -262,11 +255,7 @@ def distance(f0, f1, weight):
 class LPIPS:
     def __init__(self, canon, device="cuda"):
         """canon: the tensors of normalize_state_dict / parts_state_dict; weights are packed here, once"""
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("lpips (MI355X build): the metric lives on a GPU; there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = network_device(device, "lpips", "metric")
         self._keep = []
         w = self._weights = nat.SgrLpipsWeights()
         for i in range(5):
@@ -278,7 +267,7 @@ class LPIPS:
         for c in range(3):
             w.shift[c], w.scale[c] = float(canon["shift"][c]), float(canon["scale"][c])
         self.launches = len(LAUNCH_NAMES)
-        self._scratch = {}
+        self._scratch = ScratchCache()
 
     @classmethod
     def from_state_dict(cls, sd, device="cuda"):
@@ -294,20 +283,9 @@ class LPIPS:
 
     def _run(self, call):
         """enqueues the launches first_launch..last_launch of the record on the current stream"""
-        with torch.cuda.device(self.device):
-            st = stream(self.device)
-            n, H, W = call.n, call.H, call.W
-            need = nat.lib().sgr_lpips_scratch_bytes(n, H, W)
-            if need == 0:
-                raise RuntimeError(f"lpips: unsupported sizes (n={n} H={H} W={W})")
-            scratch = self._scratch.pop((H, W, st), None)             # one buffer per (size, stream), grown to the largest n seen
-            if scratch is None or scratch.numel() < need:
-                scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-            while len(self._scratch) >= 4:
-                self._scratch.pop(next(iter(self._scratch)))
-            self._scratch[(H, W, st)] = scratch
-            nat.check(nat.lib().sgr_lpips_forward(C.byref(self._weights), C.byref(call), scratch.data_ptr(), scratch.numel(), st),
-                      "sgr_lpips_forward")
+        n, H, W = call.n, call.H, call.W                            # one buffer per (size, stream), grown to the largest n seen
+        run_forward(self, call, (H, W), lambda: nat.lib().sgr_lpips_scratch_bytes(n, H, W), f"lpips: unsupported sizes (n={n} H={H} W={W})",
+                    "sgr_lpips_forward", grow=True)
 
     def _call(self, n, H, W, out, levels):
         call = nat.SgrLpipsCall()
@@ -334,7 +312,7 @@ class LPIPS:
         N, _, H, W = img0.shape
         tap_sizes(H, W)
         for name, t in (("img0", img0), ("img1", img1)):
-            _gpu("lpips", name, t, (torch.float16, torch.float32, torch.float64))
+            gpu_tensor("lpips", name, t, (torch.float16, torch.float32, torch.float64))
             if t.device != self.device:
                 raise RuntimeError(f"lpips: {name} is on {t.device}, the metric on {self.device}")
         a, b = img0.detach().to(torch.float32).contiguous(), img1.detach().to(torch.float32).contiguous()

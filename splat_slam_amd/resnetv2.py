@@ -26,7 +26,8 @@ import torch
 
 from splat_slam_amd import _native as nat
 from splat_slam_amd import mono_depth as M
-from splat_slam_amd._nn_common import ScratchCache, pack_weight, round_up, stream, tensor_desc
+from splat_slam_amd._nn_common import (F16_F32, ScratchCache, gpu_tensor, network_device, pack_weight, round_up, run_forward, stream,
+                                       tensor_desc)
 
 __all__ = ["ResNetV2", "LAUNCH_NAMES", "LAYER_NAMES", "backbone_shapes", "normalize_state_dict", "standardized_f16", "pack_conv",
            "conv2d_same_f16", "group_norm_f16", "max_pool_same_f16"]
@@ -102,14 +103,6 @@ def pack_conv(w16):
     return pack_weight(w16, round_up(w16.shape[1], 8))
 
 
-def _gpu(what, name, t, dtypes=(torch.float16, torch.float32)):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{what} (MI355X build): {name} must be a GPU tensor; there is no CPU path")
-    if t.dtype not in dtypes:
-        raise RuntimeError(f"{what}: {name} must be one of {dtypes}, got {t.dtype}")
-    return t
-
-
 # ---- the single kernels ----------------------------------------------------------------------------------------------------------------
 def conv2d_same_f16(x, w, stride=1, padding="same", bias=None, act="none", out_dtype=torch.float16):
     """act(conv2d(x, w, bias)) on sgr_resnet_conv: x [B,cin,h,w] and w [cout,cin,k,k] (k = 1, 3 or 7; cout a multiple of 16) are rounded
@@ -117,7 +110,7 @@ def conv2d_same_f16(x, w, stride=1, padding="same", bias=None, act="none", out_d
     padding.  act: none, relu.  The result [B,cout,ho,wo] is out_dtype (fp16 or fp32)."""
     what = "resnetv2.conv2d_same_f16"
     for name, t in (("x", x), ("w", w)) + ((("bias", bias),) if bias is not None else ()):
-        _gpu(what, name, t)
+        gpu_tensor(what, name, t, F16_F32)
     if act not in nat.SGR_RESNET_ACTS:
         raise RuntimeError(f"{what}: act must be one of {sorted(nat.SGR_RESNET_ACTS)}, got {act!r}")
     if x.dim() != 4 or w.dim() != 4 or w.shape[1] != x.shape[1] or w.shape[2] != w.shape[3] or min(x.shape) < 1:
@@ -159,7 +152,7 @@ def group_norm_f16(x, groups, gamma, beta, relu=False, residual=None):
     [B,C,h,w], a channels-last strided view."""
     what = "resnetv2.group_norm_f16"
     for name, t in (("x", x), ("gamma", gamma), ("beta", beta)) + ((("residual", residual),) if residual is not None else ()):
-        _gpu(what, name, t)
+        gpu_tensor(what, name, t, F16_F32)
     if x.dim() != 4 or min(x.shape) < 1 or tuple(gamma.shape) != (x.shape[1],) or tuple(beta.shape) != (x.shape[1],):
         raise RuntimeError(f"{what}: x [B,C,h,w] with gamma and beta [C], got {tuple(x.shape)}, {tuple(gamma.shape)}, {tuple(beta.shape)}")
     if residual is not None and residual.shape != x.shape:
@@ -185,7 +178,7 @@ def max_pool_same_f16(x):
     """max_pool2d(x, 3, 2) with TF "same" padding filled with -inf on sgr_resnet_maxpool: fp16 [B,C,h,w] (C a multiple of 8) -> fp16
     [B,C,ceil(h/2),ceil(w/2)], a channels-last strided view"""
     what = "resnetv2.max_pool_same_f16"
-    _gpu(what, "x", x, (torch.float16,))
+    gpu_tensor(what, "x", x, (torch.float16,))
     if x.dim() != 4 or min(x.shape) < 1:
         raise RuntimeError(f"{what}: x must be a non-empty [B,C,h,w], got {tuple(x.shape)}")
     B, ch, h, w = x.shape
@@ -201,11 +194,7 @@ class ResNetV2:
     def __init__(self, sd, cfg=M.MonoDepthConfig(), device="cuda"):
         sd = normalize_state_dict(sd, cfg)
         self.cfg = cfg
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("resnetv2 (MI355X build): the backbone lives on a GPU; there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = network_device(device, "resnetv2", "backbone")
         self._keep = []
         names = LAYER_NAMES(cfg)
         self._layers = (nat.SgrResnetLayer * len(names))()
@@ -233,12 +222,9 @@ class ResNetV2:
 
     def _prepare(self, x):
         """checks the argument, allocates the outputs and fills the call record: (record, the three [B, h * w, C] buffers)"""
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise RuntimeError("resnetv2 (MI355X build): x must be a GPU tensor; there is no CPU path")
+        gpu_tensor("resnetv2", "x", x, F16_F32, "fp16 or fp32")
         if x.device != self.device:
             raise RuntimeError(f"resnetv2: x is on {x.device}, the backbone on {self.device}")
-        if x.dtype not in (torch.float16, torch.float32):
-            raise RuntimeError(f"resnetv2: x must be fp16 or fp32, got {x.dtype}")
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[0] < 1 or x.shape[2] < 32 or x.shape[2] % 32 or x.shape[3] < 32 or x.shape[3] % 32:
             raise ValueError(f"resnetv2: x must be [B,3,H,W] with H and W positive multiples of 32, got {tuple(x.shape)}")
         B, _, H, W = x.shape
@@ -254,14 +240,9 @@ class ResNetV2:
 
     def _run(self, call):
         """enqueues the launches first_launch..last_launch of the record on the current stream"""
-        with torch.cuda.device(self.device):
-            st = stream(self.device)
-            n, H, W = call.n, call.H, call.W
-            scratch = self._scratch.get((n, H, W, st), self.device,
-                                        lambda: nat.lib().sgr_resnet_scratch_bytes(n, H, W, self.cfg.stem_chs, *self.cfg.stage_chs),
-                                        f"resnetv2: unsupported sizes (n={n} H={H} W={W})")
-            nat.check(nat.lib().sgr_resnet_forward(C.byref(self._weights), C.byref(call), scratch.data_ptr(), scratch.numel(), st),
-                      "sgr_resnet_forward")
+        n, H, W = call.n, call.H, call.W
+        run_forward(self, call, (n, H, W), lambda: nat.lib().sgr_resnet_scratch_bytes(n, H, W, self.cfg.stem_chs, *self.cfg.stage_chs),
+                    f"resnetv2: unsupported sizes (n={n} H={H} W={W})", "sgr_resnet_forward")
 
     def channels_last(self, x):
         call, outs = self._prepare(x)

@@ -25,7 +25,8 @@ import numpy as np
 import torch
 
 from splat_slam_amd import _native as nat
-from splat_slam_amd._nn_common import ScratchCache, pack_bias, pack_weight, round_up, stream, tensor_desc
+from splat_slam_amd._nn_common import (F16_F32, ScratchCache, gpu_tensor, network_device, pack_bias, pack_weight, round_up, run_forward, stream,
+                                       tensor_desc)
 from splat_slam_amd._nn_common import hash_uniform as _hash_uniform      # its name here before the networks shared it
 
 __all__ = ["UpdateOperator", "synthetic_state_dict", "normalize_state_dict", "conv2d_f16", "LAYER_SHAPES"]
@@ -87,10 +88,7 @@ def conv2d_f16(x, w, b=None, act="none", out_dtype=torch.float16):
     """act(conv2d(x, w, b)) with zero padding (k - 1) / 2 and stride 1: x [B,cin,h,w] and w [cout,cin,k,k] (k = 1, 3 or 7) are rounded to
     fp16, the sums are fp32, the result [B,cout,h,w] is out_dtype (fp16 or fp32).  act: none, relu, sigmoid, tanh."""
     for name, t in (("x", x), ("w", w)) + ((("b", b),) if b is not None else ()):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError(f"update_op.conv2d_f16 (MI355X build): {name} must be a GPU tensor; there is no CPU path")
-        if t.dtype not in (torch.float16, torch.float32):
-            raise RuntimeError(f"update_op.conv2d_f16: {name} must be fp16 or fp32, got {t.dtype}")
+        gpu_tensor("update_op.conv2d_f16", name, t, F16_F32, "fp16 or fp32")
     if act not in nat.SGR_UPDATE_ACTS:
         raise RuntimeError(f"update_op.conv2d_f16: act must be one of {sorted(nat.SGR_UPDATE_ACTS)}, got {act!r}")
     if out_dtype not in (torch.float16, torch.float32):
@@ -133,11 +131,7 @@ LAUNCH_NAMES = ("pack", "corr_encoder.0", "corr_encoder.2", "flow_encoder.0", "f
 class UpdateOperator:
     def __init__(self, sd, device="cuda"):
         sd = normalize_state_dict(sd)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("update_op (MI355X build): the operator lives on a GPU; there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = network_device(device, "update_op", "operator")
         self._keep = []
         self._weights = nat.SgrUpdateWeights()
         for i, (names, cin_pad) in enumerate(_PACKED):
@@ -167,12 +161,9 @@ class UpdateOperator:
         for name, t, ch in (("net", net, HIDDEN), ("inp", inp, HIDDEN), ("corr", corr, CORR_PLANES), ("flow", flow, FLOW_PLANES)):
             if t is None and name == "flow":
                 continue
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise RuntimeError(f"update_op (MI355X build): {name} must be a GPU tensor; there is no CPU path")
+            gpu_tensor("update_op", name, t, F16_F32, "fp16 or fp32")
             if t.device != self.device:
                 raise RuntimeError(f"update_op: {name} is on {t.device}, the operator on {self.device}")
-            if t.dtype not in (torch.float16, torch.float32):
-                raise RuntimeError(f"update_op: {name} must be fp16 or fp32, got {t.dtype}")
             if t.dim() != 5 or t.shape[0] != 1 or t.shape[2] != ch:
                 raise RuntimeError(f"update_op: {name} must be [1,E,{ch},h,w], got {tuple(t.shape)}")
             if t.shape[1] < 1 or t.shape[3] < 1 or t.shape[4] < 1:
@@ -211,13 +202,9 @@ class UpdateOperator:
 
     def _run(self, call):
         """enqueues the launches first_launch..last_launch of the record on the current stream"""
-        with torch.cuda.device(self.device):
-            st = stream(self.device)
-            E, K, h, w = call.E, call.K, call.h, call.w
-            scratch = self._scratch.get((E, K, h, w, st), self.device, lambda: nat.lib().sgr_update_scratch_bytes(E, K, h, w),
-                                        f"update_op: unsupported sizes (E={E} K={K} h={h} w={w})")
-            nat.check(nat.lib().sgr_update_forward(C.byref(self._weights), C.byref(call), scratch.data_ptr(), scratch.numel(), st),
-                      "sgr_update_forward")
+        E, K, h, w = call.E, call.K, call.h, call.w
+        run_forward(self, call, (E, K, h, w), lambda: nat.lib().sgr_update_scratch_bytes(E, K, h, w),
+                    f"update_op: unsupported sizes (E={E} K={K} h={h} w={w})", "sgr_update_forward")
 
     def __call__(self, net, inp, corr, flow=None, ii=None, jj=None):
         call, outs, _ = self._prepare(net, inp, corr, flow, ii)

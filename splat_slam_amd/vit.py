@@ -28,7 +28,7 @@ import torch.nn.functional as F
 
 from splat_slam_amd import _native as nat
 from splat_slam_amd import _nn_common
-from splat_slam_amd._nn_common import ScratchCache, stream
+from splat_slam_amd._nn_common import ScratchCache, gpu_tensor, network_device, run_forward, stream
 
 __all__ = ["VitConfig", "VisionTransformer", "synthetic_state_dict", "normalize_state_dict", "state_shapes", "resize_pos_embed",
            "hash_uniform", "layernorm", "gemm", "attention", "launch_names"]
@@ -125,9 +125,8 @@ def launch_names(depth):
 
 
 def _gpu(name, t, dtype):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"vit (MI355X build): {name} must be a GPU tensor; there is no CPU path")
-    if t.dtype != dtype or not t.is_contiguous():
+    """gpu_tensor for the one dtype a kernel takes, and contiguous"""
+    if not gpu_tensor("vit", name, t, (dtype,), f"contiguous {dtype}").is_contiguous():
         raise RuntimeError(f"vit: {name} must be contiguous {dtype}, got {t.dtype}")
     return t
 
@@ -195,11 +194,7 @@ class VisionTransformer:
     def __init__(self, sd, cfg=VitConfig(), device="cuda"):
         sd = normalize_state_dict(sd, cfg)
         self.cfg = cfg
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("vit (MI355X build): the transformer lives on a GPU; there is no CPU path")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = network_device(device, "vit", "transformer")
         self._keep = []
 
         def f16(key):
@@ -269,13 +264,9 @@ class VisionTransformer:
 
     def _run(self, call):
         """enqueues the launches first_launch..last_launch of the record on the current stream"""
-        with torch.cuda.device(self.device):
-            st = stream(self.device)
-            B, T = call.B, 1 + call.gh * call.gw
-            scratch = self._scratch.get((B, T, st), self.device, lambda: nat.lib().sgr_vit_scratch_bytes(B, T, self.cfg.heads, self.cfg.depth),
-                                        f"vit: unsupported sizes (B={B} T={T})")
-            nat.check(nat.lib().sgr_vit_forward(C.byref(self._weights), C.byref(call), scratch.data_ptr(), scratch.numel(), st),
-                      "sgr_vit_forward")
+        B, T = call.B, 1 + call.gh * call.gw
+        run_forward(self, call, (B, T), lambda: nat.lib().sgr_vit_scratch_bytes(B, T, self.cfg.heads, self.cfg.depth),
+                    f"vit: unsupported sizes (B={B} T={T})", "sgr_vit_forward")
 
     def __call__(self, patch_features):
         call, outs, _ = self._prepare(patch_features)
