@@ -28,6 +28,9 @@
  *                          -> the eval_mesh branch of the same function (eval_utils.py:174-187: run_evaluation of
  *                             evaluate_3d_reconstruction_lib, distance_thresh 0.05, icp_align=True): surface sampling, exact nearest
  *                             neighbours, point-to-point ICP sums and the accuracy / completion reductions
+ *   sgr_traj_*             -> src/utils/eval_traj.py: the camera centres and the skip rule of align_kf_traj (:20-55) and align_full_traj
+ *                             (:57-80), the sums behind evo's PoseTrajectory3D.align(correct_scale=True) (umeyama_alignment), and the
+ *                             errors and statistics of traj_eval_and_plot (:83-110: APE of the translation part, get_all_statistics)
  *   sgr_adam_step          -> torch.optim.Adam(eps=1e-15) over the GaussianModel groups,
  *                             thirdparty/gaussian_splatting/scene/gaussian_model.py:264-313, stepped at
  *                             src/mapper.py:352,557,703
@@ -1305,6 +1308,35 @@ int sgr_lpips_maxpool(const void* src, int32_t n, int32_t h, int32_t w, int32_t 
 int sgr_lpips_distance(const void* maps, int32_t n, int32_t P, int32_t C, const float* weight, float* partials, float* per_pixel,
                        void* stream);
 int sgr_lpips_forward(const SgrLpipsWeights* weights, const SgrLpipsCall* call, void* scratch, size_t scratch_bytes, void* stream);
+
+/* Trajectory scoring (src/utils/eval_traj.py; DESIGN.md section 3, "Trajectory scoring").  Stream-ordered, no allocation, fixed-order
+ * fp64 reductions (per-workgroup partials in `scratch`, merged in workgroup order; no float atomics): bitwise reproducible.
+ * 1 <= n <= SGR_TRAJ_MAX_POSES pairs; scratch: sgr_traj_scratch_bytes(n) bytes (0 = unsupported n), for both calls.
+ * sgr_traj_accumulate (SGR_TRAJ_ACCUMULATE_LAUNCHES launches): pair i is (row i of est, row i of ref).
+ *   est, kind SGR_TRAJ_POSE7_W2C: [est_rows, 7] (tx,ty,tz,qx,qy,qz,qw) world -> camera, the video's layout, read in place; the centre is
+ *     the translation of SE3(p).inv() in the fp32 arithmetic of se3_inv, widened to fp64.  Kind SGR_TRAJ_MAT4_C2W: [est_rows, 16]
+ *     row-major camera -> world, 16-byte aligned; the centre is (m[3], m[7], m[11]).
+ *   inds: NULL (rows 0 .. n-1 of est) or a HOST list [n] of est rows; an entry outside [0, est_rows) is SGR_ERR_INVALID before anything
+ *     is launched.  The list is copied into scratch on the stream: it stays valid until the stream has passed the call.
+ *   ref: [n, 16] row-major camera -> world, 16-byte aligned; a pair is skipped iff any of the 16 entries is not finite (eval_traj.py:30-33,
+ *     63-66: the sum of the matrix is nan or inf exactly then).
+ *   pos [n,2,3]: the centre x of the estimate and y of the reference of every pair (skipped ones too); valid [n]: 1 = used.
+ *   sums[17] over the used pairs: count, sum x (3), sum y (3), then about the means xm = sum x / count, ym = sum y / count:
+ *     sum |x - xm|^2, sum (y - ym)(x - xm)^T (9, row-major, the index of y first).
+ * sgr_traj_errors (SGR_TRAJ_ERRORS_LAUNCHES launches): sim3 = (s, R row-major (9), t (3)) on the host, read before the call returns.
+ *   err[n]: |s R x + t - y| of the used pairs, NaN for skipped ones.  stats[8] over the used pairs: count, sum e, sum e^2, min, max, the
+ *   order statistics of rank (count - 1) / 2 and count / 2 (each exactly an element of err; equal for an odd count), and
+ *   sum (e - sum e / count)^2.  With no used pair the sums are 0 and the other five NaN. */
+#define SGR_TRAJ_POSE7_W2C 0
+#define SGR_TRAJ_MAT4_C2W 1
+#define SGR_TRAJ_MAX_POSES 65535
+#define SGR_TRAJ_ACCUMULATE_LAUNCHES 2
+#define SGR_TRAJ_ERRORS_LAUNCHES 2
+size_t sgr_traj_scratch_bytes(int32_t n);
+int sgr_traj_accumulate(int32_t kind, const float* est, int32_t est_rows, SGR_HOST const int64_t* inds, int32_t n, const float* ref,
+                        double* pos, uint8_t* valid, double* sums, void* scratch, size_t scratch_bytes, void* stream);
+int sgr_traj_errors(int32_t n, const double* pos, const uint8_t* valid, SGR_HOST const double* sim3, double* err, double* stats,
+                    void* scratch, size_t scratch_bytes, void* stream);
 
 /* SE3 ops, batched over n. Pose =(tx,ty,tz,qx,qy,qz,qw) as in lietorch / depth_video.py:69; tau = (rho, theta). */
 int se3_exp(const float* tau, int64_t n, float* pose_out, void* stream);

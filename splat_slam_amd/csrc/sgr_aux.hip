@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "sgr_common.h"
+#include "sgr_se3_device.h"
 
 namespace sgr {
 int set_error(int code, const char* fmt, ...);
@@ -685,27 +686,7 @@ static size_t knn_grid_scratch_bytes(int n) {
 }
 
 // ------------------------------------------------------------------------------------------------ SE3
-struct Pose { float t[3]; float q[4]; };   // q = (x, y, z, w)
-__device__ __forceinline__ Pose load_pose(const float* p) { return {{p[0], p[1], p[2]}, {p[3], p[4], p[5], p[6]}}; }
-__device__ __forceinline__ void store_pose(float* p, const Pose& a) {
-  p[0] = a.t[0]; p[1] = a.t[1]; p[2] = a.t[2]; p[3] = a.q[0]; p[4] = a.q[1]; p[5] = a.q[2]; p[6] = a.q[3];
-}
-__device__ __forceinline__ void quat_rotate(const float q[4], const float v[3], float out[3]) {
-  // v + 2w (u x v) + 2 u x (u x v),  u = (x,y,z)
-  float ux = q[0], uy = q[1], uz = q[2], w = q[3];
-  float cx = uy * v[2] - uz * v[1], cy = uz * v[0] - ux * v[2], cz = ux * v[1] - uy * v[0];
-  float dx = uy * cz - uz * cy, dy = uz * cx - ux * cz, dz = ux * cy - uy * cx;
-  out[0] = v[0] + 2.f * (w * cx + dx);
-  out[1] = v[1] + 2.f * (w * cy + dy);
-  out[2] = v[2] + 2.f * (w * cz + dz);
-}
-__device__ __forceinline__ void quat_mul(const float a[4], const float b[4], float o[4]) {
-  o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-  o[1] = a[3] * b[1] - a[0] * b[2] + a[1] * b[3] + a[2] * b[0];
-  o[2] = a[3] * b[2] + a[0] * b[1] - a[1] * b[0] + a[2] * b[3];
-  o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-}
-
+// (Pose, quat_rotate, quat_mul, pose_inv: sgr_se3_device.h)
 enum Se3Op { OP_EXP, OP_LOG, OP_INV, OP_MUL, OP_ACT, OP_ADJT, OP_MATRIX };
 
 template <int OP>
@@ -768,12 +749,7 @@ __global__ void __launch_bounds__(256) se3_kernel(int64_t n, const float* __rest
     float* o = out + 6 * i;
     for (int k2 = 0; k2 < 3; ++k2) { o[k2] = p.t[k2] - 0.5f * c1[k2] + D * c2[k2]; o[3 + k2] = th[k2]; }
   } else if (OP == OP_INV) {
-    Pose p = load_pose(a + 7 * i), r;
-    r.q[0] = -p.q[0]; r.q[1] = -p.q[1]; r.q[2] = -p.q[2]; r.q[3] = p.q[3];
-    float rt[3];
-    quat_rotate(r.q, p.t, rt);
-    r.t[0] = -rt[0]; r.t[1] = -rt[1]; r.t[2] = -rt[2];
-    store_pose(out + 7 * i, r);
+    store_pose(out + 7 * i, pose_inv(load_pose(a + 7 * i)));
   } else if (OP == OP_MUL) {
     Pose x = load_pose(a + 7 * i), y = load_pose(b + 7 * i), r;
     quat_mul(x.q, y.q, r.q);

@@ -461,4 +461,30 @@ __device__ __forceinline__ float wave_sum(float v) {   // total in every lane
   return readlane_f(v, 63);
 }
 
+// ---- fixed-order fp64 reductions (sgr_mesh_eval.hip, sgr_traj.hip): lanes by butterfly, then the waves left to right
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+// out[k] = the sum of acc[k] over the workgroup of WAVES waves, written by thread k < N (out: global memory or LDS; for readers
+// other than thread k a barrier follows).  Every thread of the workgroup calls it.
+template <int N, int WAVES = 4>
+__device__ __forceinline__ void block_partials(double (&acc)[N], double* __restrict__ out) {
+  __shared__ double red[WAVES][N];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const double s = wave_sum_f64(acc[k]);
+    if (lane == 0) red[wv][k] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < N) {
+    double s = red[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) s += red[w][threadIdx.x];
+    out[threadIdx.x] = s;
+  }
+}
+
 }  // namespace sgr

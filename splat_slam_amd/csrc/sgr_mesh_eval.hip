@@ -353,26 +353,7 @@ __global__ void __launch_bounds__(kThreads) nn_query_kernel(int nq, const float*
   else { dist[t] = sqrtf(best); idx[t] = (int32_t)bi; }
 }
 
-// ---- fixed-order reductions
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-template <int N>
-__device__ __forceinline__ void block_partials(double (&acc)[N], double* __restrict__ out) {
-  __shared__ double red[4][N];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    const double s = wave_sum_f64(acc[k]);
-    if (lane == 0) red[wv][k] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < N) out[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-}
-
+// ---- fixed-order reductions (wave_sum_f64, block_partials: sgr_common.h)
 __global__ void __launch_bounds__(kThreads) icp_partial_kernel(int n, const float* __restrict__ src, NnXform T, const int32_t* __restrict__ idx,
                                                                int nt, const float* __restrict__ tgt, double* __restrict__ parts) {
   double acc[kIcpSums];

@@ -17,9 +17,28 @@ section 3, "Slam".
 On a keyframe: its mono map goes into the depth cache (prepared once), KeyframeDepth.get fuses it with the video's current state, and
 the result goes to session.process -- or, with fewer than 100 valid tracker pixels, the camera is registered as no mapping keyframe
 (mapper.py:910-926).  When a keyframe is mapped, the session asks for the current pose and depth of all past keyframes: they come from
-one batched fusion call (the pose source's prefetch).  The mono-depth network is splat_slam_amd.mono_depth.MonoDepth, itself such a callable.  Not provided: dataset loaders, trajectory
-scoring, logging.
+one batched fusion call (the pose source's prefetch).  The mono-depth network is splat_slam_amd.mono_depth.MonoDepth, itself such a callable.
+
+    slam.evaluate(gt_poses=None, gt_depths=None, mesh=False, gt_mesh_path=None, lpips=None, out_dir=None) -> dict
+        after terminate(): the rest of the reference's terminate() (slam.py:169-242) in its order, on splat_slam_amd.traj_eval.
+        gt_poses: camera -> world 4x4 per frame of the stream, indexed by timestamp (default stream.poses when the stream has one).
+        "kf_traj": the ATE statistics of the keyframes after the scaled Umeyama alignment (kf_traj_eval), "global_scale", "r_a", "t_a":
+        that alignment; "rendering": eval_rendering over the session's viewpoints (what session.evaluate runs) with the mapped cameras
+        moved into the ground-truth frame (aligned_c2w) as c2w and with global_scale (None without a map); "depth_l1":
+        video.eval_depth_l1 per frame aligned and with global_scale, when stream[i][2] is a depth (None otherwise); "full_traj",
+        "full_traj_alignment", "traj_est": full_traj_eval over a PoseTrajectoryFiller of the same net and video (the video needs 16
+        free slots behind its keyframes).  Without ground-truth poses the trajectory entries are
+        None, global_scale is 1 and the cameras keep their own poses.  A trajectory that determines no similarity
+        (TrajectoryDegenerate) is reported under "traj_error" / "full_traj_error" and scored with scale 1 and the identity; the
+        rendering evaluation still runs (the reference swallows the exception and then fails on an unbound name).  out_dir: video.npz
+        (with `scale`), metrics_kf_traj.txt, metrics_full_traj.txt and, with mesh, mesh.ply are written there.
+
+Not provided: dataset loaders, plots, logging.
 """
+import os
+import tempfile
+
+import numpy as np
 import torch
 
 from splat_slam_amd.backend import Backend
@@ -95,3 +114,54 @@ class Slam:
             return []
         self.session.refresh_keyframes()
         return self.session.finish()
+
+    def evaluate(self, gt_poses=None, gt_depths=None, mesh=False, gt_mesh_path=None, lpips=None, out_dir=None):
+        from splat_slam_amd import traj_eval
+        from splat_slam_amd.trajectory_filler import PoseTrajectoryFiller
+        if gt_poses is None:
+            gt_poses = getattr(self.stream, "poses", None)
+        out = {"kf_traj": None, "global_scale": 1.0, "r_a": None, "t_a": None, "rendering": None, "depth_l1": None, "full_traj": None,
+               "full_traj_alignment": None, "traj_est": None}
+        npz = None
+        if out_dir is not None:
+            os.makedirs(out_dir, exist_ok=True)
+            npz = os.path.join(out_dir, "video.npz")
+            self.video.save_video(npz)
+        alignment = None
+        if gt_poses is not None:
+            try:
+                out["kf_traj"], s, r_a, t_a = traj_eval.kf_traj_eval(self.video, gt_poses, out_dir=out_dir, npz_path=npz)
+                alignment = traj_eval.Alignment(r_a, t_a, s, 0, 0)
+                out["global_scale"], out["r_a"], out["t_a"] = s, r_a, t_a
+            except traj_eval.TrajectoryDegenerate as e:
+                out["traj_error"] = str(e)
+        if not self.session.init:                      # there is a map: MappingSession.evaluate's call, with the two aligned arguments
+            from splat_slam_amd.eval import eval_rendering
+            from splat_slam_amd.mapper import PipelineParams
+            loop = self.session.loop
+            frames = [loop.viewpoints[k] for k in sorted(loop.viewpoints)]
+            c2w = None if alignment is None else list(traj_eval.aligned_c2w(frames, alignment))
+            out["rendering"] = eval_rendering(
+                frames, loop.gaussians, PipelineParams(), loop.background, gt_depths=gt_depths, global_scale=out["global_scale"],
+                mesh=mesh, mesh_path=os.path.join(out_dir, "mesh.ply") if (mesh and out_dir is not None) else None, c2w=c2w,
+                gt_mesh_path=gt_mesh_path, lpips=lpips)
+        if self.video.counter.value > 0 and hasattr(self.stream, "__getitem__") and self.stream[0][2] is not None:
+            out["depth_l1"] = self._depth_l1(out["global_scale"], npz)
+        if gt_poses is not None:
+            try:
+                out["traj_est"], out["full_traj"], out["full_traj_alignment"] = traj_eval.full_traj_eval(
+                    PoseTrajectoryFiller(self.net, self.video, device=self.video.device), self.stream, gt_poses, out_dir=out_dir)
+            except traj_eval.TrajectoryDegenerate as e:
+                out["full_traj_error"] = str(e)
+        return out
+
+    def _depth_l1(self, global_scale, npz):
+        """slam.py:206-216: the sensor-depth error of the video's depth maps, per frame aligned and with the trajectory's scale"""
+        with tempfile.TemporaryDirectory() as tmp:
+            if npz is None:                            # eval_depth_l1 reads the timestamps of a save_video file only
+                npz = os.path.join(tmp, "video.npz")
+                np.savez(npz, timestamps=self.video.timestamp[:self.video.counter.value].cpu().numpy())
+            l1, l1_4m, coverage = self.video.eval_depth_l1(npz, self.stream)
+            l1_g, l1_4m_g, _ = self.video.eval_depth_l1(npz, self.stream, global_scale)
+        return {"depth_l1": float(l1), "depth_l1_mask_4m": float(l1_4m), "coverage": float(coverage),
+                "depth_l1_global_scale": float(l1_g), "depth_l1_mask_4m_global_scale": float(l1_4m_g)}
