@@ -31,6 +31,8 @@
  *   sgr_traj_*             -> src/utils/eval_traj.py: the camera centres and the skip rule of align_kf_traj (:20-55) and align_full_traj
  *                             (:57-80), the sums behind evo's PoseTrajectory3D.align(correct_scale=True) (umeyama_alignment), and the
  *                             errors and statistics of traj_eval_and_plot (:83-110: APE of the translation part, get_all_statistics)
+ *   sgr_frame_prepare      -> BaseDataset.__getitem__ / get_color of src/utils/datasets.py:133-216: cv2.undistort, cv2.resize, / 255, the
+ *                             nearest resize of the depth and the crop of the edge (the project's own integer arithmetic, not OpenCV's bits)
  *   sgr_adam_step          -> torch.optim.Adam(eps=1e-15) over the GaussianModel groups,
  *                             thirdparty/gaussian_splatting/scene/gaussian_model.py:264-313, stepped at
  *                             src/mapper.py:352,557,703
@@ -1337,6 +1339,26 @@ int sgr_traj_accumulate(int32_t kind, const float* est, int32_t est_rows, SGR_HO
                         double* pos, uint8_t* valid, double* sums, void* scratch, size_t scratch_bytes, void* stream);
 int sgr_traj_errors(int32_t n, const double* pos, const uint8_t* valid, SGR_HOST const double* sim3, double* err, double* stats,
                     void* scratch, size_t scratch_bytes, void* stream);
+
+/* Frame preparation of the dataset streams (src/utils/datasets.py:170-216; DESIGN.md section 3, "Datasets and frame preparation"):
+ * undistortion, bilinear resize to (H_oe, W_oe), crop of the edge and / 255 of the colour, nearest resize, crop and / depth_scale of the
+ * depth, for n >= 1 frames of one camera in SGR_FRAME_PREPARE_LAUNCHES launch.  Stream-ordered, no scratch, every output element written.
+ *   color_u8 [n,H,W,ps]: ps = 3 or 4 bytes a pixel, R G B first (with ps = 4 the fourth byte is ignored and color_u8 is 4-byte aligned).
+ *   depth_u16 [n,H,W] and out_depth [n,H_out,W_out] are given together or both NULL.  H_out = H_oe - 2 H_edge, W_out = W_oe - 2 W_edge.
+ *   map_q [H,W,2] int32, 8-byte aligned, or NULL (no undistortion): (qx, qy) of every full-size pixel, the source position in 1/32 pixel.
+ *   Colour, in integers: U(v,u,c) = (sum w p + 512) >> 10 over the taps (iy,ix), (iy,ix+1), (iy+1,ix), (iy+1,ix+1) with ix = qx >> 5,
+ *   ax = qx & 31 (iy, ay likewise), weights (32-ax)(32-ay), ax(32-ay), (32-ax)ay, ax ay, a tap outside the image counting as 0; without
+ *   a map U is the source level.  Per axis of input size S and output size D, output index j has n = (2j+1) S - D, d = 2D, s = floor(n/d),
+ *   b = floor((4096 (n - s d) + d) / (2d)); s < 0 gives s = 0, b = 0; s >= S-1 gives s = S-1, b = 0 and the second tap at S-1.
+ *   R = (sum_y sum_x wy wx U + 2^21) >> 22 with w in {2048 - b, b}; out_color[c][y][x] = (float)R(y + H_edge, x + W_edge, c) / 255.0f.
+ *   Depth: sy = min((int)floorf((y + H_edge) * ((float)H / (float)H_oe)), H - 1), sx likewise, out = (float)d / depth_scale: the bits of
+ *   torch's F.interpolate(mode="nearest") on the CPU, then the crop.  Both fp32 divisions are correctly rounded.
+ *   SGR_ERR_INVALID (nothing launched): n outside [1, 65535], a side outside [1, 16384], edges that leave no pixel, ps not 3 or 4, depth
+ *   given on one side only or with a depth_scale that is not positive and finite, a misaligned pointer. */
+#define SGR_FRAME_PREPARE_LAUNCHES 1
+int sgr_frame_prepare(int32_t n, const uint8_t* color_u8, int32_t ps, const uint16_t* depth_u16, int32_t H, int32_t W, const int32_t* map_q,
+                      int32_t H_oe, int32_t W_oe, int32_t H_edge, int32_t W_edge, float depth_scale, float* out_color, float* out_depth,
+                      void* stream);
 
 /* SE3 ops, batched over n. Pose =(tx,ty,tz,qx,qy,qz,qw) as in lietorch / depth_video.py:69; tau = (rho, theta). */
 int se3_exp(const float* tau, int64_t n, float* pose_out, void* stream);

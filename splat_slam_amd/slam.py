@@ -33,7 +33,8 @@ one batched fusion call (the pose source's prefetch).  The mono-depth network is
         rendering evaluation still runs (the reference swallows the exception and then fails on an unbound name).  out_dir: video.npz
         (with `scale`), metrics_kf_traj.txt, metrics_full_traj.txt and, with mesh, mesh.ply are written there.
 
-Not provided: dataset loaders, plots, logging.
+`stream` for a Replica, ScanNet or TUM RGB-D folder: splat_slam_amd.datasets.get_dataset(splat_slam_amd.config.load_config(...)).
+Not provided: plots, logging.
 """
 import os
 import tempfile
