@@ -424,6 +424,48 @@ int sgr_icp_accumulate(int32_t n, const float* source, SGR_HOST const float* tra
 int sgr_cloud_metrics(int32_t na, const float* dist_a, int32_t nb, const float* dist_b, float thresh, double* out, void* scratch,
                       size_t scratch_bytes, void* stream);
 
+/* Culling a mesh to what a set of cameras saw, before it is scored ("Mesh culling"): a frustum test, an
+ * occlusion test against depth rendered from the mesh itself, faces of unseen vertices dropped.  Frames come in chunks of at most
+ * SGR_CULL_MAX_FRAMES.  Pixel centres sit at integer (u, v); coordinates are snapped to 2^-SGR_CULL_SUBPIXEL_BITS pixel.
+ * sgr_cull_project: per (vertex, frame) in fp64, p = w2c (x, y, z, 1), u = fx p.x / p.z + cx, v = fy p.y / p.z + cy;
+ *   xy[n,V,2] = llrint(256 u), llrint(256 v) and z[n,V] = (float)p.z.  A vertex with p.z < near, anything non-finite, |u| or |v|
+ *   beyond SGR_CULL_GUARD_PIXELS or a p.z that fp32 holds as 0 or inf is invalid: z = 0, xy = 0.
+ * sgr_cull_raster: the z-buffer depth[n,H,W] of the triangles from xy and z: +inf where nothing is hit, else the minimum over the
+ *   covering triangles of the perspective-correct depth A / (E0/z0 + E1/z1 + E2/z2) (fp32).  Coverage is exact on the snapped
+ *   coordinates: pixel (i, j) is covered when the three edge functions at (256 j, 256 i) are >= 0 after orienting the triangle to
+ *   doubled area A > 0 (inclusive, both windings; A = 0 is skipped).  The result does not depend on the order of the triangles.  A
+ *   triangle with an invalid vertex is not drawn (there is no near-plane clipping) and counted in skipped[n] when not NULL.
+ *   H, W <= SGR_CULL_GUARD_PIXELS.  scratch: sgr_cull_raster_bytes(F, n).
+ * sgr_cull_visibility: seen[v] += the number of the n frames that see vertex v: z > 0, z <= far, pixel j = (x + 128) >> 8,
+ *   i = (y + 128) >> 8 with edge <= j < W - edge and edge <= i < H - edge and, with a depth map (depth[n,H,W], or NULL: frustum
+ *   only) d at that pixel, !(d > 0) || z - d <= eps (one fp32 subtraction): zero, negative and NaN depth constrain nothing.
+ * sgr_cull_select: a face is kept when all three (SGR_CULL_RULE_ALL) or any (SGR_CULL_RULE_ANY) of its vertices have
+ *   seen >= min_views; vertices that no kept face references are dropped; totals[0..1] = kept (vertices, triangles) on the device.
+ *   sgr_cull_compact, with the same scratch (sgr_cull_select_bytes(V, F)), writes them in their original order, reindexed, and
+ *   vertex_map[V] (new index or -1) when not NULL. */
+#define SGR_CULL_MAX_FRAMES 16
+#define SGR_CULL_SUBPIXEL_BITS 8
+#define SGR_CULL_GUARD_PIXELS 16384
+#define SGR_CULL_RULE_ALL 0
+#define SGR_CULL_RULE_ANY 1
+typedef struct SgrCullFrame {
+  double w2c[12];              /* host, row-major 3x4 world -> camera */
+  double fx, fy, cx, cy;
+} SgrCullFrame;
+int sgr_cull_project(int32_t V, const float* vertices, int32_t n, const SgrCullFrame* frames, double near, int32_t* xy, float* z,
+                     void* stream);
+size_t sgr_cull_raster_bytes(int32_t F, int32_t n);
+int sgr_cull_raster(int32_t V, int32_t F, const int32_t* triangles, int32_t n, const int32_t* xy, const float* z, int32_t H, int32_t W,
+                    float* depth, int32_t* skipped, void* scratch, size_t scratch_bytes, void* stream);
+int sgr_cull_visibility(int32_t V, int32_t n, const int32_t* xy, const float* z, const float* depth, int32_t H, int32_t W, int32_t edge,
+                        float far, float eps, int32_t* seen, void* stream);
+size_t sgr_cull_select_bytes(int32_t V, int32_t F);
+int sgr_cull_select(int32_t V, int32_t F, const int32_t* triangles, const int32_t* seen, int32_t min_views, int32_t rule, void* scratch,
+                    size_t scratch_bytes, int32_t* totals, void* stream);
+int sgr_cull_compact(int32_t V, int32_t F, const float* vertices, const float* colors, const int32_t* triangles, void* scratch,
+                     size_t scratch_bytes, float* out_vertices, float* out_colors, int32_t* out_triangles, int32_t* vertex_map,
+                     void* stream);
+
 /* One torch.optim.Adam step (no weight decay, no amsgrad) on a flat parameter slab. step = the value AFTER
  * increment (1 on the first call).  lr may differ per call (update_learning_rate, gaussian_model.py:315-329). */
 int sgr_adam_step(int64_t n, float* param, const float* grad, float* exp_avg, float* exp_avg_sq,

@@ -7,6 +7,9 @@ mesh (:70-74, 142-179, clean_mesh :331-379) from the HIP kernels of splat_slam_a
 scores that mesh (:174-187: accuracy, completion, completion ratio, precision, F-score and chamfer-L1 after ICP alignment) on the
 HIP kernels of splat_slam_amd.mesh_eval.  Given an `splat_slam_amd.lpips.LPIPS` object, eval_rendering also reports LPIPS (:66-68, 125,
 192) from the HIP kernels of splat_slam_amd.lpips; the project ships no trained AlexNet weights, the object loads the caller's."""
+import functools
+import inspect
+
 import numpy as np
 import torch
 
@@ -43,6 +46,33 @@ def _device_depth(d, device):
     return d.to(dtype=torch.float32, device=device).reshape(d.shape[-2:]).contiguous()
 
 
+def _with_mesh_culling(fn):
+    """eval_rendering plus two opt-in keywords, as a stage around the function: cull_mesh=True scores the meshes after culling them.
+    The function itself, its parameter list and its defaults stay what tests/test_lpips_cpu.py pins."""
+    @functools.wraps(fn)
+    def eval_rendering(*args, cull_mesh=False, cull_poses=None, **kwargs):
+        a = inspect.signature(fn).bind(*args, **kwargs)
+        a.apply_defaults()
+        a = a.arguments
+        if not (cull_mesh and a["mesh"] and a["eval_mesh"] and a["gt_mesh_path"] is not None):
+            return fn(*args, **kwargs)
+        result = fn(**{**a, "eval_mesh": False})
+        from splat_slam_amd.mesh_eval import evaluate_mesh
+        frames = a["frames"]
+        poses = cull_poses if cull_poses is not None else a["c2w"]
+        if poses is None:
+            poses = [torch.linalg.inv(p) for p in _w2c(frames)]
+        try:
+            pred, gt = _culled(result, result["mesh"], a["gt_mesh_path"], frames, poses)
+            result["mesh_metrics"] = evaluate_mesh(pred, gt, distance_thresh=a["distance_thresh"], icp_align=a["icp_align"],
+                                                   samples=a["mesh_samples"])
+        except ValueError as e:
+            result["mesh_metrics_error"] = str(e)
+        return result
+    return eval_rendering
+
+
+@_with_mesh_culling
 @torch.no_grad()
 def eval_rendering(frames, gaussians, pipe, background, gt_depths=None, global_scale=1.0, mesh=False, mesh_path=None, c2w=None,
                    voxel_length=5.0 / 512.0, sdf_trunc=0.04, eval_mesh=True, gt_mesh_path=None, distance_thresh=0.05, icp_align=True,
@@ -64,7 +94,13 @@ def eval_rendering(frames, gaussians, pipe, background, gt_depths=None, global_s
     eval_mesh with a ground-truth mesh gt_mesh_path (a PLY path or a TriangleMesh; :174-187): the result also gains "mesh_metrics",
     splat_slam_amd.mesh_eval.evaluate_mesh(mesh, gt, distance_thresh, icp_align, samples=mesh_samples), or, where that raises
     ValueError (e.g. a mesh without a triangle of positive area), "mesh_metrics_error" with its message, as the reference's
-    try/except does.  Without a ground-truth mesh the result is what it is without these arguments."""
+    try/except does.  Without a ground-truth mesh the result is what it is without these arguments.
+    Two more keywords, cull_mesh=False and cull_poses=None (_with_mesh_culling; nothing is culled by default): with cull_mesh=True and
+    a ground-truth mesh, the cleaned mesh and the ground truth are both culled, before they are scored, to what the poses cull_poses
+    (camera -> world 4x4 each; default the fusion poses) see, by splat_slam_amd.mesh_cull.cull_mesh with the frames' intrinsics and
+    size (frame k's for pose k when there is one pose per frame, else the first frame's) and occlusion from each mesh's own depth.
+    The result gains "mesh_cull" ({"pred", "gt"}: the counts of cull_mesh's info) and "gt_mesh_culled"; "mesh" and the written PLY
+    stay the unculled mesh.  A culled mesh without faces ends in "mesh_metrics_error"."""
     if not frames:
         raise ValueError("eval_rendering: no frames")
     if gt_depths is not None and len(gt_depths) != len(frames):
@@ -144,6 +180,24 @@ def eval_rendering(frames, gaussians, pipe, background, gt_depths=None, global_s
             except ValueError as e:
                 result["mesh_metrics_error"] = str(e)
     return result
+
+
+def _culled(result, pred, gt, frames, c2w):
+    """both meshes culled to the poses c2w; fills result["mesh_cull"] and result["gt_mesh_culled"]"""
+    from splat_slam_amd.mesh_cull import cull_mesh
+    from splat_slam_amd.mesh_eval import _as_mesh
+    H, W = frames[0].original_image.shape[1:]
+    use = frames if len(c2w) == len(frames) else frames[:1]
+    intr = [[float(f.fx), float(f.fy), float(f.cx), float(f.cy)] for f in use]
+    gt = _as_mesh(gt, frames[0].original_image.device)
+    counts = ("vertices_before", "vertices_after", "faces_before", "faces_after", "unrasterized_triangles")
+    out, result["mesh_cull"] = [], {}
+    for name, m in (("pred", pred), ("gt", gt)):
+        culled, info = cull_mesh(m, c2w, intr, H, W, return_info=True)
+        result["mesh_cull"][name] = {k: info[k] for k in counts}
+        out.append(culled)
+    result["gt_mesh_culled"] = out[1]
+    return out
 
 
 def _w2c(frames):

@@ -19,7 +19,7 @@ the result goes to session.process -- or, with fewer than 100 valid tracker pixe
 (mapper.py:910-926).  When a keyframe is mapped, the session asks for the current pose and depth of all past keyframes: they come from
 one batched fusion call (the pose source's prefetch).  The mono-depth network is splat_slam_amd.mono_depth.MonoDepth, itself such a callable.
 
-    slam.evaluate(gt_poses=None, gt_depths=None, mesh=False, gt_mesh_path=None, lpips=None, out_dir=None) -> dict
+    slam.evaluate(gt_poses=None, gt_depths=None, mesh=False, gt_mesh_path=None, lpips=None, out_dir=None, cull_mesh=False) -> dict
         after terminate(): the rest of the reference's terminate() (slam.py:169-242) in its order, on splat_slam_amd.traj_eval.
         gt_poses: camera -> world 4x4 per frame of the stream, indexed by timestamp (default stream.poses when the stream has one).
         "kf_traj": the ATE statistics of the keyframes after the scaled Umeyama alignment (kf_traj_eval), "global_scale", "r_a", "t_a":
@@ -32,6 +32,9 @@ one batched fusion call (the pose source's prefetch).  The mono-depth network is
         (TrajectoryDegenerate) is reported under "traj_error" / "full_traj_error" and scored with scale 1 and the identity; the
         rendering evaluation still runs (the reference swallows the exception and then fails on an unbound name).  out_dir: video.npz
         (with `scale`), metrics_kf_traj.txt, metrics_full_traj.txt and, with mesh, mesh.ply are written there.
+        cull_mesh=True: eval_rendering culls the predicted and the ground-truth mesh to what the keyframes saw before it scores them
+        (splat_slam_amd.mesh_cull), from the ground-truth poses of the keyframes when there are ground-truth poses, else from the
+        fusion poses.  Nothing is culled by default.
 
 `stream` for a Replica, ScanNet or TUM RGB-D folder: splat_slam_amd.datasets.get_dataset(splat_slam_amd.config.load_config(...)).
 Not provided: plots, logging.
@@ -116,7 +119,7 @@ class Slam:
         self.session.refresh_keyframes()
         return self.session.finish()
 
-    def evaluate(self, gt_poses=None, gt_depths=None, mesh=False, gt_mesh_path=None, lpips=None, out_dir=None):
+    def evaluate(self, gt_poses=None, gt_depths=None, mesh=False, gt_mesh_path=None, lpips=None, out_dir=None, cull_mesh=False):
         from splat_slam_amd import traj_eval
         from splat_slam_amd.trajectory_filler import PoseTrajectoryFiller
         if gt_poses is None:
@@ -142,10 +145,15 @@ class Slam:
             loop = self.session.loop
             frames = [loop.viewpoints[k] for k in sorted(loop.viewpoints)]
             c2w = None if alignment is None else list(traj_eval.aligned_c2w(frames, alignment))
+            cull = {}
+            if cull_mesh:
+                ts = self.video.timestamp.cpu().tolist()
+                cull = dict(cull_mesh=True, cull_poses=None if gt_poses is None else
+                            [gt_poses[int(ts[k])] for k in sorted(loop.viewpoints)])
             out["rendering"] = eval_rendering(
                 frames, loop.gaussians, PipelineParams(), loop.background, gt_depths=gt_depths, global_scale=out["global_scale"],
                 mesh=mesh, mesh_path=os.path.join(out_dir, "mesh.ply") if (mesh and out_dir is not None) else None, c2w=c2w,
-                gt_mesh_path=gt_mesh_path, lpips=lpips)
+                gt_mesh_path=gt_mesh_path, lpips=lpips, **cull)
         if self.video.counter.value > 0 and hasattr(self.stream, "__getitem__") and self.stream[0][2] is not None:
             out["depth_l1"] = self._depth_l1(out["global_scale"], npz)
         if gt_poses is not None:
