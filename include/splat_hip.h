@@ -31,6 +31,8 @@
  *   sgr_traj_*             -> src/utils/eval_traj.py: the camera centres and the skip rule of align_kf_traj (:20-55) and align_full_traj
  *                             (:57-80), the sums behind evo's PoseTrajectory3D.align(correct_scale=True) (umeyama_alignment), and the
  *                             errors and statistics of traj_eval_and_plot (:83-110: APE of the translation part, get_all_statistics)
+ *   sgr_plot_*             -> the per-keyframe figure of the same function (eval_utils.py:131-135, plot_rgbd_silhouette): the six cells,
+ *                             their titles and the heading as one RGB panel
  *   sgr_frame_prepare      -> BaseDataset.__getitem__ / get_color of src/utils/datasets.py:133-216: cv2.undistort, cv2.resize, / 255, the
  *                             nearest resize of the depth and the crop of the edge (the project's own integer arithmetic, not OpenCV's bits)
  *   sgr_adam_step          -> torch.optim.Adam(eps=1e-15) over the GaussianModel groups,
@@ -1401,6 +1403,49 @@ int sgr_traj_errors(int32_t n, const double* pos, const uint8_t* valid, SGR_HOST
 int sgr_frame_prepare(int32_t n, const uint8_t* color_u8, int32_t ps, const uint16_t* depth_u16, int32_t H, int32_t W, const int32_t* map_q,
                       int32_t H_oe, int32_t W_oe, int32_t H_edge, int32_t W_edge, float depth_scale, float* out_color, float* out_depth,
                       void* stream);
+
+/* The per-keyframe figure of eval_rendering (src/utils/eval_utils.py:131-135, plot_rgbd_silhouette; DESIGN.md section 3, "Plots"): for
+ * each of n frames one RGB panel of 2 x 3 cells, ground truth above the render: colour, depth, difference.  Each cell shows its image
+ * reduced by the integer factor s: a source pixel is first turned into the byte triple a full-size plot would show, a cell pixel is the
+ * integer mean (sum + cnt / 2) / cnt per channel over its s x s block, cnt the pixels of the block that exist.  Source pixels:
+ *   (0,0) (int)(255 clamp(gt, 0, 1));  (1,0) the same of clamp(exp(a) render + b, 0, 1), the image of sgr_render_metrics;
+ *   (0,1) jet(gt_depth / depth_max);   (1,1) jet((global_scale * depth) / depth_max);
+ *   (0,2) jet index min(255, 256 e / max e), e = the sum over the channels of |level of (0,0) - level of (1,0)|, in integers;
+ *   (1,2) jet(e / max e), e = |global_scale * depth - gt_depth| where depth > 0 and gt_depth > 0, else 0.
+ * jet(t) is entry clamp((int)floor(256 t), 0, 255) of the 256-entry jet table; every product, difference and quotient above is one
+ * correctly rounded fp32 operation.  A maximum is taken over the frame's finite values and 0 gives t = 0; a value that is not finite
+ * is drawn white.  Layout: white background; the heading at (SGR_PLOT_MARGIN, SGR_PLOT_MARGIN), clipped at PW - SGR_PLOT_MARGIN; cell
+ * (r, c) of size ch x cw = ceil(H / s) x ceil(W / s) has its left edge at SGR_PLOT_MARGIN + c (cw + SGR_PLOT_MARGIN), its title's top at
+ * 2 SGR_PLOT_MARGIN + SGR_PLOT_CHAR_H + r (SGR_PLOT_CHAR_H + SGR_PLOT_TITLE_GAP + ch + SGR_PLOT_MARGIN) and its image
+ * SGR_PLOT_CHAR_H + SGR_PLOT_TITLE_GAP below that; a title is clipped at its cell's right edge.  Text is black, one 5 x 7 glyph at
+ * twice its size in the top left of each SGR_PLOT_CHAR_W x SGR_PLOT_CHAR_H character cell; a text ends at its first NUL or after
+ * SGR_PLOT_TEXT - 1 bytes, and a byte outside 32 .. 126 is drawn as '?'.
+ * sgr_plot_panel_size: host arithmetic only; PH = PW = 0 for H, W outside [1, 16384] or s < 1.
+ * sgr_plot_panels: `frames` is a host array, copied into scratch on the stream: it stays valid until the stream has passed the call.
+ * SGR_PLOT_LAUNCHES launches per SGR_PLOT_MAX_FRAMES frames (the maxima by integer atomicMax, order-independent; the composition, every
+ * output byte written once); a frame's panel is the same alone and in any batch.  depth and gt_depth are required; exposure_a / _b as
+ * in SgrMetricFrame.  SGR_ERR_INVALID / SGR_ERR_WORKSPACE before anything is launched. */
+#define SGR_PLOT_MAX_FRAMES 16
+#define SGR_PLOT_LAUNCHES 2
+#define SGR_PLOT_TEXT 64
+#define SGR_PLOT_MARGIN 8
+#define SGR_PLOT_CHAR_W 12
+#define SGR_PLOT_CHAR_H 16
+#define SGR_PLOT_TITLE_GAP 4
+typedef struct SgrPlotFrame {
+  const float* render;         /* [3,H,W] */
+  const float* gt_image;       /* [3,H,W] */
+  const float* depth;          /* [H,W] rendered depth */
+  const float* gt_depth;       /* [H,W] */
+  const float* exposure_a;     /* device scalar, or NULL */
+  const float* exposure_b;     /* device scalar, or NULL */
+  char heading[SGR_PLOT_TEXT];
+  char titles[6 * SGR_PLOT_TEXT];    /* cell (r, c) at 64 (3 r + c) */
+} SgrPlotFrame;
+void sgr_plot_panel_size(int32_t H, int32_t W, int32_t s, SGR_HOST int32_t* PH, SGR_HOST int32_t* PW);
+size_t sgr_plot_scratch_bytes(int32_t n);
+int sgr_plot_panels(int32_t n, const SgrPlotFrame* frames, int32_t H, int32_t W, int32_t s, float global_scale, float depth_max,
+                    uint8_t* panels, void* scratch, size_t scratch_bytes, void* stream);
 
 /* SE3 ops, batched over n. Pose =(tx,ty,tz,qx,qy,qz,qw) as in lietorch / depth_video.py:69; tau = (rho, theta). */
 int se3_exp(const float* tau, int64_t n, float* pose_out, void* stream);

@@ -301,6 +301,17 @@ struct Layout {
   }
 };
 
+// The evaluation's image of a render (eval_utils.py:96-100): clamp(exp(a) r + b, 0, 1), the product and the sum each rounded on its
+// own: the bits of torch's exp(a) * r + b (the __fmul_rn / __fadd_rn intrinsics do not keep the compiler from fusing them).  What
+// sgr_mesh.hip fuses, sgr_lpips.hip packs and sgr_plot.hip draws; ea = exp(a) or 1, eb = b or 0.
+__device__ __forceinline__ float exposed_image(float ea, float r, float eb) {
+#pragma clang fp contract(off)
+  const float scaled = ea * r;
+  return fminf(fmaxf(scaled + eb, 0.f), 1.f);
+}
+// ... and its colour level, (image * 255) truncated: the reference's (x * 255).astype(uint8)
+__device__ __forceinline__ int color_level(float image) { return (int)(image * 255.f); }
+
 // per-view pointers of the fused mapping loss (sgr_mapping_loss / sgr_map_views)
 struct LossTab {
   const float* image[kMaxViews];

@@ -50,10 +50,7 @@ __global__ void __launch_bounds__(kThreads) lpips_pack_kernel(const PackTab t, h
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     float x = src[(int64_t)c * t.HW + o];
-    if (expose) {
-      const float scaled = ea * x;
-      x = fminf(fmaxf(scaled + eb, 0.f), 1.f);
-    }
+    if (expose) x = exposed_image(ea, x, eb);
     if (t.normalize) x = 2.f * x - 1.f;
     v[c] = (half_t)((x - t.shift[c]) / t.scale[c]);
   }

@@ -129,13 +129,9 @@ __device__ inline float frame_depth(const FrameDev& f, int o, float depth_trunc)
   return d > depth_trunc ? 0.f : d;
 }
 
-// colour byte of channel c: (clamp(exp(a) r + b, 0, 1) * 255) truncated; a multiply, an add and a multiply, each rounded on its
-// own: the bits of torch's exp(a) * r + b (the __fmul_rn / __fadd_rn intrinsics do not keep the compiler from fusing them)
+// colour byte of channel c: (clamp(exp(a) r + b, 0, 1) * 255) truncated (exposed_image, color_level of sgr_common.h)
 __device__ inline float frame_color(const FrameDev& f, float ea, float eb, int c, size_t HW, int o) {
-#pragma clang fp contract(off)
-  const float scaled = ea * f.render[c * HW + o];
-  const float img = fminf(fmaxf(scaled + eb, 0.f), 1.f);
-  return (float)(int)(img * kColorScale);
+  return (float)color_level(exposed_image(ea, f.render[c * HW + o], eb));
 }
 
 // ---- touch: thread = sampled pixel of one frame (grid.y)

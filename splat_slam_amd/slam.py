@@ -19,7 +19,8 @@ the result goes to session.process -- or, with fewer than 100 valid tracker pixe
 (mapper.py:910-926).  When a keyframe is mapped, the session asks for the current pose and depth of all past keyframes: they come from
 one batched fusion call (the pose source's prefetch).  The mono-depth network is splat_slam_amd.mono_depth.MonoDepth, itself such a callable.
 
-    slam.evaluate(gt_poses=None, gt_depths=None, mesh=False, gt_mesh_path=None, lpips=None, out_dir=None, cull_mesh=False) -> dict
+    slam.evaluate(gt_poses=None, gt_depths=None, mesh=False, gt_mesh_path=None, lpips=None, out_dir=None, cull_mesh=False,
+                  plots=False) -> dict
         after terminate(): the rest of the reference's terminate() (slam.py:169-242) in its order, on splat_slam_amd.traj_eval.
         gt_poses: camera -> world 4x4 per frame of the stream, indexed by timestamp (default stream.poses when the stream has one).
         "kf_traj": the ATE statistics of the keyframes after the scaled Umeyama alignment (kf_traj_eval), "global_scale", "r_a", "t_a":
@@ -35,9 +36,13 @@ one batched fusion call (the pose source's prefetch).  The mono-depth network is
         cull_mesh=True: eval_rendering culls the predicted and the ground-truth mesh to what the keyframes saw before it scores them
         (splat_slam_amd.mesh_cull), from the ground-truth poses of the keyframes when there are ground-truth poses, else from the
         fusion poses.  Nothing is culled by default.
+        plots=True (needs out_dir, ValueError otherwise): the two trajectory evaluations also write kf_traj.png and full_traj.png, and after
+        eval_rendering, splat_slam_amd.plots.plot_rendering writes plots_after_refine/video_idx_{V}_kf_idx_{T}.png per mapped viewpoint (T
+        the keyframe's timestamp as an integer) and output.gif from that result.  The returned dict is the same.  Nothing is drawn by default.
 
 `stream` for a Replica, ScanNet or TUM RGB-D folder: splat_slam_amd.datasets.get_dataset(splat_slam_amd.config.load_config(...)).
-Not provided: plots, logging.
+The command line and the output tree: splat_slam_amd.run.  Not provided: a mode without a mapper (--only_tracking),
+eval_before_final_ba, predict_online: False.
 """
 import os
 import tempfile
@@ -119,9 +124,13 @@ class Slam:
         self.session.refresh_keyframes()
         return self.session.finish()
 
-    def evaluate(self, gt_poses=None, gt_depths=None, mesh=False, gt_mesh_path=None, lpips=None, out_dir=None, cull_mesh=False):
+    def evaluate(self, gt_poses=None, gt_depths=None, mesh=False, gt_mesh_path=None, lpips=None, out_dir=None, cull_mesh=False,
+                 plots=False):
         from splat_slam_amd import traj_eval
         from splat_slam_amd.trajectory_filler import PoseTrajectoryFiller
+        if plots and out_dir is None:
+            raise ValueError("Slam.evaluate(plots=True) needs out_dir: the figures are files")
+        plot = {"plot": True} if plots else {}
         if gt_poses is None:
             gt_poses = getattr(self.stream, "poses", None)
         out = {"kf_traj": None, "global_scale": 1.0, "r_a": None, "t_a": None, "rendering": None, "depth_l1": None, "full_traj": None,
@@ -134,7 +143,7 @@ class Slam:
         alignment = None
         if gt_poses is not None:
             try:
-                out["kf_traj"], s, r_a, t_a = traj_eval.kf_traj_eval(self.video, gt_poses, out_dir=out_dir, npz_path=npz)
+                out["kf_traj"], s, r_a, t_a = traj_eval.kf_traj_eval(self.video, gt_poses, out_dir=out_dir, npz_path=npz, **plot)
                 alignment = traj_eval.Alignment(r_a, t_a, s, 0, 0)
                 out["global_scale"], out["r_a"], out["t_a"] = s, r_a, t_a
             except traj_eval.TrajectoryDegenerate as e:
@@ -154,12 +163,18 @@ class Slam:
                 frames, loop.gaussians, PipelineParams(), loop.background, gt_depths=gt_depths, global_scale=out["global_scale"],
                 mesh=mesh, mesh_path=os.path.join(out_dir, "mesh.ply") if (mesh and out_dir is not None) else None, c2w=c2w,
                 gt_mesh_path=gt_mesh_path, lpips=lpips, **cull)
+            if plots:
+                from splat_slam_amd.plots import plot_rendering
+                ts = self.video.timestamp.cpu().tolist()
+                names = [f"video_idx_{k}_kf_idx_{int(ts[k])}" for k in sorted(loop.viewpoints)]
+                plot_rendering(frames, loop.gaussians, PipelineParams(), loop.background, out["rendering"],
+                               os.path.join(out_dir, "plots_after_refine"), names, gt_depths=gt_depths, global_scale=out["global_scale"])
         if self.video.counter.value > 0 and hasattr(self.stream, "__getitem__") and self.stream[0][2] is not None:
             out["depth_l1"] = self._depth_l1(out["global_scale"], npz)
         if gt_poses is not None:
             try:
                 out["traj_est"], out["full_traj"], out["full_traj_alignment"] = traj_eval.full_traj_eval(
-                    PoseTrajectoryFiller(self.net, self.video, device=self.video.device), self.stream, gt_poses, out_dir=out_dir)
+                    PoseTrajectoryFiller(self.net, self.video, device=self.video.device), self.stream, gt_poses, out_dir=out_dir, **plot)
             except traj_eval.TrajectoryDegenerate as e:
                 out["full_traj_error"] = str(e)
         return out

@@ -13,8 +13,9 @@ conventions assumed about it.  No plots (evo.tools.plot has no counterpart here)
         t_a [3], s, n_used, n_skipped and `pairs`, the device state that ape() scores.
     ape(alignment, pairs=None) -> {rmse, mean, median, std, min, max, sse}
         evo's statistics of |s r_a x + t_a - y| over the used pairs; alignment None scores `pairs` (pair_centres) as they are.
-    kf_traj_eval(video, gt_poses, out_dir=None, npz_path=None) -> (stats, s, r_a, t_a)         eval_traj.py:113-140
-    full_traj_eval(filler, stream, gt_poses, out_dir=None) -> (traj_unaligned [T,4,4], stats, alignment)     eval_traj.py:143-175
+    kf_traj_eval(video, gt_poses, out_dir=None, npz_path=None, plot=False) -> (stats, s, r_a, t_a)         eval_traj.py:113-140
+    full_traj_eval(filler, stream, gt_poses, out_dir=None, plot=False) -> (traj_unaligned [T,4,4], stats, alignment)     eval_traj.py:143-175
+        plot=True with an out_dir also writes kf_traj.png / full_traj.png beside the metrics file; the return values are the same.
     aligned_c2w(cameras_or_c2w, alignment) -> [K,4,4] fp64       slam.py:145-152: PosePath3D.scale(s), then .transform(se3(r_a, t_a))
 
 GPU tensors only for the poses: there is no CPU path.  One read-back per align and one per ape.
@@ -213,7 +214,12 @@ def _report(title, alignment, stats, path):
     return text
 
 
-def kf_traj_eval(video, gt_poses, out_dir=None, npz_path=None):
+def _plot(alignment, out_dir, name, title):
+    from splat_slam_amd.plots import plot_trajectory
+    plot_trajectory(alignment, os.path.join(out_dir, name), title)
+
+
+def kf_traj_eval(video, gt_poses, out_dir=None, npz_path=None, plot=False):
     """The keyframes of `video` against gt_poses[int(video.timestamp[i])] (camera -> world 4x4 each): video.poses[:counter] is scored in
     place.  Both trajectories come from one timestamp list, so evo's association step is the identity and is not restated.  With out_dir,
     metrics_kf_traj.txt is written there; with npz_path (a DepthVideo.save_video file), `scale` is added to it (eval_traj.py:137-138)."""
@@ -224,6 +230,8 @@ def kf_traj_eval(video, gt_poses, out_dir=None, npz_path=None):
     alignment = align(video.poses[:n], _gt_rows(gt_poses, ts, video.poses.device), POSE7_W2C)
     stats = ape(alignment)
     _report("Keyframes traj", alignment, stats, None if out_dir is None else os.path.join(out_dir, "metrics_kf_traj.txt"))
+    if plot and out_dir is not None:
+        _plot(alignment, out_dir, "kf_traj.png", "Keyframes traj")
     if npz_path is not None:
         saved = dict(np.load(npz_path))
         saved["scale"] = np.array(alignment.s)
@@ -232,7 +240,7 @@ def kf_traj_eval(video, gt_poses, out_dir=None, npz_path=None):
 
 
 @torch.no_grad()
-def full_traj_eval(filler, stream, gt_poses, out_dir=None):
+def full_traj_eval(filler, stream, gt_poses, out_dir=None, plot=False):
     """Every frame of the stream: the filler's poses with the keyframes' rows overwritten by the video's (a device index copy, as
     eval_traj.py:148-151 does on the host), aligned to gt_poses[i] and scored.  Returns the unaligned camera -> world trajectory
     [T,4,4] (device), the statistics and the Alignment; with out_dir, metrics_full_traj.txt is written there."""
@@ -246,4 +254,6 @@ def full_traj_eval(filler, stream, gt_poses, out_dir=None):
     alignment = align(traj, _gt_rows(gt_poses, range(T), traj.device), POSE7_W2C)
     stats = ape(alignment)
     _report("Full traj", alignment, stats, None if out_dir is None else os.path.join(out_dir, "metrics_full_traj.txt"))
+    if plot and out_dir is not None:
+        _plot(alignment, out_dir, "full_traj.png", "Full traj")
     return lietorch.SE3(traj).inv().matrix(), stats, alignment
