@@ -280,17 +280,25 @@ int sgr_query_list_histogram(const SgrWorkspace* ws, int32_t num_gaussians, int3
  *     testing its Gaussians one by one (a map that grows keyframe by keyframe is spatially coherent: whole segments miss
  *     whole views).  Conservative: results are identical either way.  Off by default because it does not pay on MI355X:
  *     preprocess_fwd is bound by its counting atomics and output writes, not by the per-Gaussian visibility arithmetic
- *     (measured on a keyframe-ordered 300 k map: 65.6 us with, 64.7 us without). */
+ *     (measured on a keyframe-ordered 300 k map: 65.6 us with, 64.7 us without).
+ *   SGR_OPT_ADAM_IN_K1 (default 1; SGR_ADAM_IN_K1=0 in the environment, read once, also turns it off): inside sgr_map_run the
+ *     optimiser step of every iteration but the last is not a launch of its own: the blocks of the next iteration's forward
+ *     preprocess run it for their own 256 Gaussians before they start (bitwise identical results) -- where that launch has one
+ *     block per segment, i.e. on maps large enough to fill the chip that way (sgr_common.h: k1_parts_for).  0: every step is
+ *     launched on its own, the sequence sgr_map_step gives.  2: on every map; the forward preprocess of such an iteration then
+ *     runs with one block per segment whatever the map's size (tests and experiments on small maps). */
 #define SGR_OPT_FUSED_BLEND 0
 #define SGR_OPT_UPSTREAM_POSE_JACOBIAN 1
 #define SGR_OPT_SEGMENT_TEST 2
-#define SGR_OPT_COUNT 3
+#define SGR_OPT_ADAM_IN_K1 3
+#define SGR_OPT_COUNT 4
 int sgr_set_option(int32_t option, int32_t value);
 int sgr_get_option(int32_t option);
 
-/* Per-kernel HIP-event timing.  kind: 0 preprocess_fwd (+ binning), 1 tile_scan, 2 scatter, 3 fused tile kernel (blend
- * forward + loss + blend backward), 4 blend_fwd (+ in-wave tile sort), 5 blend_bwd, 6 preprocess_bwd (+ gather / optimiser
- * pass, pose reduce).  sgr_profile_enable(mask) arms event pairs around the kinds whose
+/* Per-kernel HIP-event timing.  kind: 0 preprocess_fwd (+ binning; + the previous iteration's optimiser step where the launch
+ * carries it, SGR_OPT_ADAM_IN_K1), 1 tile_scan, 2 scatter, 3 fused tile kernel (blend
+ * forward + loss + blend backward), 4 blend_fwd (+ in-wave tile sort), 5 blend_bwd, 6 preprocess_bwd (+ gather, pose reduce)
+ * and the optimiser pass where it is a launch of its own (a record of its own).  sgr_profile_enable(mask) arms event pairs around the kinds whose
  * bit is set (0 disarms); sgr_profile_read() synchronises, returns accumulated milliseconds and launch counts per
  * kind since the last read, and resets them. Events are recorded on the stream the kernel is launched on. */
 #define SGR_PROFILE_KINDS 7

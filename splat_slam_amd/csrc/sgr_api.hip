@@ -13,9 +13,10 @@
 
 namespace sgr {
 
-void launch_preprocess_fwd(const ViewTab&, int, const LOff&, const Common&, const SgrInputs&, hipStream_t);
+void launch_preprocess_fwd(const ViewTab&, int, const LOff&, const Common&, const SgrInputs&, hipStream_t, const K1Adam* adam = nullptr);
+bool k1_can_run_adam(const LOff&, int);
 void launch_preprocess_bwd(const ViewTab&, int, const LOff&, const Common&, const SgrInputs&, const SgrGradInputs&, const FusedAdam*,
-                           hipStream_t, bool mapping_loop = false);
+                           hipStream_t, bool mapping_loop = false, bool defer_adam = false);
 void launch_binning(const ViewTab&, int, const LOff&, hipStream_t);
 void launch_zero_heads(const ViewTab&, int, const LOff&, size_t, hipStream_t);
 void launch_blend_fwd(const ViewTab&, int, const LOff&, const float*, const LossTab*, const LossCoef*, hipStream_t);
@@ -24,7 +25,7 @@ void launch_blend_fused(const ViewTab&, int, const LOff&, const float*, const Lo
 bool blend_can_fuse(const LOff&);
 
 // run-time options (sgr_set_option)
-static int g_opt[SGR_OPT_COUNT] = {1, 0, 0};
+static int g_opt[SGR_OPT_COUNT] = {1, 0, 0, 1};
 
 static thread_local char g_err[512] = "";
 int set_error(int code, const char* fmt, ...) {
@@ -47,6 +48,37 @@ int debug_flags() {
 }
 
 static Layout make_layout(int N, int H, int W, int64_t cap) { return Layout(N, H, W, cap); }
+
+// SGR_OPT_ADAM_IN_K1 / SGR_ADAM_IN_K1=0 in the environment (read once) / -DSGR_ADAM_IN_K1=0: off = every optimiser step of
+// sgr_map_run is a gather_adam_kernel launch of its own
+// 1: where K1 has one block per segment anyway (k1_parts_for: maps large enough to fill the chip)   2: everywhere -- K1 then runs
+// with one block per segment whatever k1_parts_for says (small maps lose their view parts: for tests and experiments)
+static int adam_in_k1_level() {
+  static const int env = []() { const char* e = getenv("SGR_ADAM_IN_K1"); return e ? atoi(e) : 1; }();
+  return (SGR_ADAM_IN_K1 != 0 && env != 0) ? g_opt[SGR_OPT_ADAM_IN_K1] : 0;
+}
+static bool adam_in_k1_ok(const LOff& d, int nv) {
+  const int level = adam_in_k1_level();
+  return level >= 2 ? d.N > 0 : (level == 1 && k1_can_run_adam(d, nv));
+}
+
+// The optimiser step an iteration of sgr_map_run left to the next iteration's K1 (K1Adam, sgr_common.h).  Whoever launches the
+// next kernel on the stream either hands it to K1 or launches it first (flush_adam): the stream order of today's sequence.
+struct AdamCarry {
+  bool allow = false;       // the running iteration may leave its step behind (it is not the last of the run)
+  bool pending = false;
+  int iter = -1, owner = -1;   // running iteration / the iteration `step` belongs to
+  K1Adam step;
+  LOff L;                   // of the step's iteration
+};
+static void flush_adam(AdamCarry* c, hipStream_t st) {
+  if (!c || !c->pending) return;
+  ViewTab tab = {};
+  for (int v = 0; v < c->step.av.nviews; ++v) { tab.saved[v] = c->step.av.saved[v]; tab.scratch[v] = c->step.av.scratch[v]; tab.radii[v] = c->step.av.radii[v]; }
+  ProfScope prof(PK_PRE_BWD, st);
+  launch_gather_adam(tab, c->step.av.nviews, c->L, c->step.fa, st);
+  c->pending = false;
+}
 
 // ---- event-pair profiler
 struct ProfState {
@@ -163,13 +195,13 @@ static void tab_set_view(ViewTab& t, int v, const SgrSettings* s, const SgrOutpu
 
 // forward of a batch that shares N, H, W, capacity and the view-independent settings
 static int forward_batch(const ViewTab& tab, int nviews, const Layout& L, const Common& cm, const SgrInputs& in, hipStream_t st,
-                         bool counters_clean = false, int max_list_hint = 0) {
+                         bool counters_clean = false, int max_list_hint = 0, const K1Adam* adam = nullptr) {
   LOff d = L.dev();
   d.set_hint(max_list_hint);
   // header + per-tile pair counters; tile_scan re-zeroes the counters after reading them, so only blocks that never
   // went through a forward (or the caller does not vouch for) need this launch
   if (!counters_clean) launch_zero_heads(tab, nviews, d, L.zero_bytes, st);
-  launch_preprocess_fwd(tab, nviews, d, cm, in, st);     // K1: project, footprint, count pairs per tile
+  launch_preprocess_fwd(tab, nviews, d, cm, in, st, adam);     // K1: project, footprint, count pairs per tile (+ a carried optimiser step)
   launch_binning(tab, nviews, d, st);                    // K2: tile/block scans   K3: scatter keys
   return SGR_OK;
 }
@@ -352,7 +384,7 @@ int sgr_backward_views(int32_t num_views, const SgrBackwardView* views, const Sg
 // pair over the rendered images (groups of term->max_views views) and leaves float pixel gradients; NULL = the L1 epilogue.
 static int map_views_impl(int32_t num_views, const SgrMapView* views, const SgrInputs* in, const SgrGradInputs* grads, float alpha,
                           float rgb_boundary_threshold, int32_t forward_only, FusedAdam* fused, bool* fused_done,
-                          void* stream, bool store_sinks = false, const SgrSsimTerm* term = nullptr) {
+                          void* stream, bool store_sinks = false, const SgrSsimTerm* term = nullptr, AdamCarry* carry = nullptr) {
   if (fused_done) *fused_done = false;
   if (num_views < 0 || (num_views > 0 && (!views || !in)) || (!forward_only && !grads))
     return set_error(SGR_ERR_INVALID, "map_views: null argument");
@@ -393,6 +425,7 @@ static int map_views_impl(int32_t num_views, const SgrMapView* views, const SgrI
     if (!forward_only && grads && !grads->accumulate && num_views > 1)
       return set_error(SGR_ERR_INVALID, "map_views: several views need accumulate != 0");
   }
+  if (!uniform || f.settings.num_gaussians == 0 || store_sinks || num_views > kMaxViews) flush_adam(carry, st);
   if (store_sinks && !forward_only && grads && !(fused && uniform && f.settings.num_gaussians > 0 && num_views <= kMaxViews)) {
     const size_t n = (size_t)f.settings.num_gaussians, m = (size_t)(f.settings.sh_coeffs > 0 ? f.settings.sh_coeffs : 1);
     if (grads->dL_dmeans3D) HIP_TRY(hipMemsetAsync(grads->dL_dmeans3D, 0, n * 12, st));
@@ -460,7 +493,21 @@ static int map_views_impl(int32_t num_views, const SgrMapView* views, const SgrI
         lt.parts[v] = m.loss_scratch;
       }
     }
-    if (int rc = forward_batch(tab, nv, L, cm, *in, st, all_clean, d.mean_hint)) return rc;
+    // a step the previous iteration left behind rides in K1 where K1 has one block per segment, nobody zeroes the headers whose
+    // `overflow` it reads (launch_zero_heads) and the layout is the one its records were written in; otherwise it is launched first
+    const K1Adam* ride = nullptr;
+    if (carry && carry->pending) {
+      if (adam_in_k1_ok(d, nv) && all_clean && !forward_only && !term && carry->L.N == d.N &&
+          carry->L.H == d.H && carry->L.W == d.W && carry->L.cap == d.cap)
+        ride = &carry->step;
+      else
+        flush_adam(carry, st);
+    }
+    if (int rc = forward_batch(tab, nv, L, cm, *in, st, all_clean, d.mean_hint, ride)) return rc;
+    if (ride) {
+      carry->pending = false;
+      d.k1_parts = 1;          // (that launch has one block per segment: this iteration's vismask is one word per Gaussian)
+    }
     if (forward_only) {
       launch_blend_fwd(tab, nv, d, f.settings.bg, nullptr, nullptr, st);
       continue;
@@ -496,7 +543,16 @@ static int map_views_impl(int32_t num_views, const SgrMapView* views, const SgrI
     }
     if (term) launch_blend_bwd(tab, nv, d, f.settings.bg, nullptr, nullptr, st);      // float pixel gradients
     else if (!fused_blend) launch_blend_bwd(tab, nv, d, f.settings.bg, &lt, &lc, st);
-    launch_preprocess_bwd(tab, nv, d, cm, *in, *grads, fuse ? fused : nullptr, st, /*mapping_loop=*/true);
+    // not the last iteration of a sgr_map_run: the optimiser pass is not launched, the next iteration's K1 runs it
+    const bool defer = fuse && carry && carry->allow && !term && fused->gather_only == 0 && adam_in_k1_ok(d, nv);
+    launch_preprocess_bwd(tab, nv, d, cm, *in, *grads, fuse ? fused : nullptr, st, /*mapping_loop=*/true, defer);
+    if (defer) {
+      carry->step.fa = *fused;
+      for (int v = 0; v < kMaxViews; ++v) { carry->step.av.saved[v] = tab.saved[v]; carry->step.av.scratch[v] = tab.scratch[v]; carry->step.av.radii[v] = tab.radii[v]; }
+      carry->step.av.nviews = nv; carry->step.av.k1_parts = d.k1_parts;
+      carry->L = d;
+      carry->pending = true; carry->owner = carry->iter;
+    }
     if (fuse && fused_done) *fused_done = true;
   }
   HIP_TRY(hipGetLastError());
@@ -515,9 +571,10 @@ int sgr_map_views(int32_t num_views, const SgrMapView* views, const SgrInputs* i
 // One iteration.  When the Adam step directly follows the views of a uniform single-chunk batch and the gradient sinks
 // are the optimiser's own gradient buffers, gather + Adam + next activations run as ONE pass (gather_adam_kernel).
 static int map_step_impl(const SgrMapStep* p, bool skip_activate, bool grads_clean, bool allow_fuse, bool* fused_out, void* stream,
-                         const SgrSsimTerm* term = nullptr) {
+                         const SgrSsimTerm* term = nullptr, AdamCarry* carry = nullptr) {
   if (fused_out) *fused_out = false;
   if (!p) return set_error(SGR_ERR_INVALID, "map_step: null argument");
+  if (p->num_views <= 0) flush_adam(carry, (hipStream_t)stream);
   // an optimiser-only step (no views: the second half of a multi-GPU iteration, after the all-reduce) writes the
   // activations of the UPDATED parameters in the Adam pass itself instead of activating the old ones first
   const bool adam_only = p->num_views == 0 && p->adam_groups;
@@ -580,7 +637,7 @@ static int map_step_impl(const SgrMapStep* p, bool skip_activate, bool grads_cle
   bool fused = false;
   if (p->num_views > 0)
     if (int rc = map_views_impl(p->num_views, p->views, p->in, p->grads, p->alpha, p->rgb_boundary_threshold, p->forward_only,
-                                try_fuse ? &fa : nullptr, &fused, stream, p->grads_clean == -3 && !p->adam_groups, term))
+                                try_fuse ? &fa : nullptr, &fused, stream, p->grads_clean == -3 && !p->adam_groups, term, carry))
       return rc;
   if (p->adam_groups && !fused)
     if (int rc = gaussian_adam_step_act(p->num_gaussians, p->adam_groups, p->beta1, p->beta2, p->eps, p->iso_weight,
@@ -626,6 +683,7 @@ static int map_run_impl(const SgrMapRun* r, const SgrSsimTerm* term, void* strea
   st.adam_groups = r->adam_groups;
   const int32_t exp_rows = st.exp_rows;
   bool prev_fused = false;
+  AdamCarry carry;
   for (int it = 0; it < r->num_iters; ++it) {
     for (int j = 0; j < r->picks_per_iter; ++j) {
       const int32_t k = r->picks[(size_t)it * r->picks_per_iter + j];
@@ -663,11 +721,17 @@ static int map_run_impl(const SgrMapRun* r, const SgrSsimTerm* term, void* strea
     }
     // after a fused tail the activations of the updated parameters are already written and the sinks are clean
     bool fused = false;
-    if (int rc = map_step_impl(&st, prev_fused, it == 0 ? r->step.grads_clean > 0 : r->adam_groups != nullptr, r->step.grads_clean >= 0,
-                               &fused, stream, term))
-      return rc;
+    // iterations 0 .. n-2 leave their optimiser step to the next iteration's K1; the last step of a run is a launch of its own
+    // (span boundaries -- where the caller snapshots, reads headers, prunes -- see exactly today's state)
+    carry.iter = it;
+    carry.allow = it + 1 < r->num_iters && nv > 0 && nv <= kMaxViews;
+    const int rc = map_step_impl(&st, prev_fused, it == 0 ? r->step.grads_clean > 0 : r->adam_groups != nullptr, r->step.grads_clean >= 0,
+                                 &fused, stream, term, &carry);
+    if (carry.pending && (rc != SGR_OK || carry.owner != it)) flush_adam(&carry, (hipStream_t)stream);   // (an error return before any launch)
+    if (rc) return rc;
     prev_fused = fused;
   }
+  flush_adam(&carry, (hipStream_t)stream);
   return SGR_OK;
 }
 

@@ -370,6 +370,29 @@ int make_fused_adam(int64_t n, const SgrAdamGroup groups[5], float beta1, float 
 int gaussian_adam_step_act(int64_t n, const SgrAdamGroup groups[5], float beta1, float beta2, float eps, float iso_weight,
                            float* s_out, float* r_out, float* o_out, void* stream);
 void launch_gather_adam(const ViewTab& tab, int nviews, const LOff& L, const FusedAdam& fa, hipStream_t st);
+// The views whose gradient records an optimiser pass gathers: per view the workspace pair and the radii of the iteration that
+// wrote the records.  gather_adam_kernel fills it from its ViewTab; the K1 instantiation that runs the step receives it next to
+// the NEXT iteration's ViewTab (the random picks of a span change from iteration to iteration, and with them radii).
+struct AdamViews {
+  char* saved[kMaxViews];
+  char* scratch[kMaxViews];
+  int32_t* radii[kMaxViews];
+  int nviews, k1_parts;       // k1_parts: vismask words per Gaussian written by that iteration's K1
+};
+// An optimiser step that sgr_map_run did not launch on its own: the next iteration's K1 runs it, block by block, ahead of its
+// own work (preprocess_fwd_kernel<true>).  Everything BY VALUE, as built in the step's own iteration (step counters, learning
+// rate, exposure row, picks): the host has moved on by the time it runs.
+#ifndef SGR_ADAM_IN_K1
+#define SGR_ADAM_IN_K1 1      // 0: the form is compiled out (every step is a gather_adam_kernel launch)
+#endif
+struct K1Adam {
+  FusedAdam fa;
+  AdamViews av;
+  int regs;       // the step stores exactly the rows K1's phase A loads (xyz, exp(scale), normalised rotation: same pointers, groups
+                  // not skipped): the thread takes its Gaussian from the step's registers and phase A starts while the stores drain
+};
+// ViewTab (2 KB) + K1Adam + the rest of K1's arguments must fit the 4 KB kernarg segment
+static_assert(sizeof(ViewTab) + sizeof(LOff) + sizeof(Common) + 7 * sizeof(void*) + sizeof(K1Adam) + 64 <= 4096, "K1's kernarg segment");
 
 // ---- optional per-kernel event timing (sgr_profile_enable / sgr_profile_read)
 enum ProfKind { PK_PRE_FWD = 0, PK_SCAN, PK_SCATTER, PK_BLEND_FUSED, PK_BLEND_FWD, PK_BLEND_BWD, PK_PRE_BWD };

@@ -10,6 +10,7 @@
 // registers) -- HBM bytes, not flops, bound these kernels.  Per-Gaussian pose gradients are reduced in-kernel
 // (wave DPP + LDS) to one 6-vector per block, then by a fixed-order second stage: deterministic, no [N,6] buffer.
 #include "sgr_common.h"
+#include "sgr_adam_device.h"
 
 namespace sgr {
 
@@ -297,10 +298,39 @@ __device__ __forceinline__ bool maybe_visible_planes(const float p[3], float s, 
 //            pairs (-> partial-slot offsets, finished by tile_scan_kernel) and its slot in the (view, segment) visible
 //            list seg_list[seg*256 + k]; scatter_kernel later concatenates those lists.
 // Everything is fixed-order: results are bitwise reproducible.
+//
+// ADAM = true (sgr_map_run, iterations 1 .. n-1 of a span): the block FIRST runs the previous iteration's optimiser step for its own
+// 256 Gaussians -- the body of gather_adam_kernel<1|2> (sgr_adam_device.h), with that launch's rider blocks (one per view: loss sums +
+// exposure row step) as extra leading blocks of this grid -- then __syncthreads(), then K1 as above.  No block depends on another:
+// the step of segment s reads vismask / gradient records / radii of ITS range of the previous iteration's views and the views'
+// header.overflow (written by the previous K2), and reads and writes parameters, moments, statistics and activations of its range;
+// K1 of segment s reads parameters and activations of its range only, and nothing K1 writes outside its range (tile counters,
+// buckets, the overflow list, ovf_cursor / count_saturated) is read by the step.  Saves a launch whose empty grid costs 8 us, a
+// kernel boundary with tens of MB dirty in L2, and the wait for the step's stores ahead of the cull (measured: DESIGN.md section 3).
+// The inputs are NOT __restrict__ here: the step stores what phases A and B load.  Phase A takes its own Gaussian from the step's
+// registers where the step stored exactly those rows (K1Adam.regs); phase B gathers other threads' rows after phase A's barrier.
+template <bool ADAM> struct K1In { typedef const float* __restrict__ ptr; };
+template <> struct K1In<true> { typedef const float* ptr; };
+struct K1NoAdam { int unused; };
+template <bool ADAM> struct K1Step { typedef K1NoAdam type; };
+template <> struct K1Step<true> { typedef K1Adam type; };
+template <bool ADAM> struct K1Lds { typedef char type; };
+template <> struct K1Lds<true> { typedef AdamShared type; };
+
+template <bool ADAM>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))) preprocess_fwd_kernel(
-    ViewTab tab, int nviews, LOff L, Common cm, const float* __restrict__ means3D, const float* __restrict__ opacities,
-    const float* __restrict__ shs, const float* __restrict__ colors_precomp, const float* __restrict__ scales,
-    const float* __restrict__ rotations, const float* __restrict__ cov3D_precomp) {
+    ViewTab tab, int nviews, LOff L, Common cm, typename K1In<ADAM>::ptr means3D, typename K1In<ADAM>::ptr opacities,
+    typename K1In<ADAM>::ptr shs, typename K1In<ADAM>::ptr colors_precomp, typename K1In<ADAM>::ptr scales,
+    typename K1In<ADAM>::ptr rotations, typename K1In<ADAM>::ptr cov3D_precomp, typename K1Step<ADAM>::type ka) {
+  __shared__ typename K1Lds<ADAM>::type ash;
+  int nrider = 0;
+  if constexpr (ADAM) {
+    nrider = ka.fa.tail_views;
+    if ((int)blockIdx.x < nrider) {              // rider blocks (scheduled first): no dependency on any other block
+      adam_rider_view(ka.fa, ka.av.saved[blockIdx.x], (int)blockIdx.x, ash);
+      return;
+    }
+  }
   __shared__ float mats[kMaxViews][32];            // viewmatrix | projmatrix of every view
   __shared__ char* p_saved[kMaxViews];
   __shared__ int32_t* p_radii[kMaxViews];
@@ -322,7 +352,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))
   __shared__ float seg_box[4][8];                // per wave: min xyz, max xyz, max trS of its 64 Gaussians
   __shared__ uint32_t seg_views;                 // bit v = some Gaussian of this segment MAY be visible in view v
   const int N = L.N;
-  const int seg = blockIdx.x, seg0 = seg * kSeg;
+  const int seg = (int)blockIdx.x - nrider, seg0 = seg * kSeg;
   const int part = blockIdx.y, nparts = gridDim.y;      // this block's views: v % nparts == part
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
 
@@ -341,6 +371,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))
   __syncthreads();
   if (tid < nviews) cullK[tid] = cull_radius_factor(mats[tid], L.H, L.W, cm.tanfovx, cm.tanfovy);
   __syncthreads();
+  // ---- the carried optimiser step of this segment.  Phase A needs this thread's OWN Gaussian only: where the step has just stored
+  // those rows it hands them over in registers (kept[]) and phase A runs while the step's stores drain; the barrier that ends
+  // phase A orders them before phase B, which reads other threads' rows.
+  float kept[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  bool use_kept = false;
+  if constexpr (ADAM) {
+    if (ka.fa.grads_clean) gather_adam_segment<2>(ka.fa, ka.av, L, seg, ash, kept);
+    else gather_adam_segment<1>(ka.fa, ka.av, L, seg, ash, kept);
+    use_kept = ka.regs != 0;
+    if (!use_kept) __syncthreads();
+  }
 
   // ---- phase A
   const int ia = seg0 + tid;
@@ -349,13 +390,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8))
     float p[3] = {0.f, 0.f, 0.f};
     float trS = 0.f;
     if (ia < N) {
-      { const F3 t = ld3(means3D + 3 * ia); p[0] = t.x; p[1] = t.y; p[2] = t.z; }
-      if (cov3D_precomp) {
+      if (ADAM && use_kept) { p[0] = kept[0]; p[1] = kept[1]; p[2] = kept[2]; }
+      else { const F3 t = ld3(means3D + 3 * ia); p[0] = t.x; p[1] = t.y; p[2] = t.z; }
+      if (cov3D_precomp && !(ADAM && use_kept)) {
         trS = cov3D_precomp[6 * ia] + cov3D_precomp[6 * ia + 3] + cov3D_precomp[6 * ia + 5];
       } else {
-        const F3 sc3 = ld3(scales + 3 * ia);
+        F3 sc3;
+        float4 q;
+        if (ADAM && use_kept) { sc3 = F3{kept[3], kept[4], kept[5]}; q = make_float4(kept[6], kept[7], kept[8], kept[9]); }
+        else { sc3 = ld3(scales + 3 * ia); q = *(const float4*)(rotations + 4 * ia); }
         const float s0 = sc3.x, s1 = sc3.y, s2 = sc3.z;
-        const float4 q = *(const float4*)(rotations + 4 * ia);
         const float n2 = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
         if (fabsf(n2 - 1.f) < 1e-3f) {     // R(q) = (1-n2) I + n2 R(q/|q|): column norms <= 1.002
           trS = cm.mod * cm.mod * (s0 * s0 + s1 * s1 + s2 * s2) * 1.01f;
@@ -1295,17 +1339,30 @@ __global__ void __launch_bounds__(384) tau_reduce_kernel(ViewTab tab, LOff L) {
   }
 }
 
-void launch_preprocess_fwd(const ViewTab& tab, int nviews, const LOff& L, const Common& cm, const SgrInputs& in, hipStream_t st) {
+// adam: the previous iteration's optimiser step rides at the head of this launch (callers: k1_can_run_adam)
+bool k1_can_run_adam(const LOff& L, int nviews) { return SGR_ADAM_IN_K1 != 0 && L.N > 0 && min(L.k1_parts, nviews) == 1; }
+void launch_preprocess_fwd(const ViewTab& tab, int nviews, const LOff& L, const Common& cm, const SgrInputs& in, hipStream_t st,
+                           const K1Adam* adam) {
   if (L.N <= 0) return;
   ProfScope prof(PK_PRE_FWD, st);
-  hipLaunchKernelGGL(preprocess_fwd_kernel, dim3(L.nseg, min(L.k1_parts, nviews)), dim3(256), 0, st, tab, nviews, L, cm, in.means3D, in.opacities,
-                     in.shs, in.colors_precomp, in.scales, in.rotations, in.cov3D_precomp);
+#if SGR_ADAM_IN_K1
+  if (adam) {
+    K1Adam ka = *adam;
+    const AdamGroups& G = ka.fa.G;
+    ka.regs = (!in.cov3D_precomp && in.means3D == G.g[0].param && !G.g[0].skip && G.r0[0] <= 0 && G.r1[0] >= L.N && G.r0[3] <= 0 &&
+               G.r1[3] >= L.N && G.r0[4] <= 0 && G.r1[4] >= L.N && ka.fa.s_out && in.scales == ka.fa.s_out && ka.fa.r_out &&
+               in.rotations == ka.fa.r_out) ? 1 : 0;
+    hipLaunchKernelGGL(preprocess_fwd_kernel<true>, dim3(L.nseg + adam->fa.tail_views, 1), dim3(256), 0, st, tab, nviews, L, cm, in.means3D,
+                       in.opacities, in.shs, in.colors_precomp, in.scales, in.rotations, in.cov3D_precomp, ka);
+    return;
+  }
+#endif
+  hipLaunchKernelGGL(preprocess_fwd_kernel<false>, dim3(L.nseg, min(L.k1_parts, nviews)), dim3(256), 0, st, tab, nviews, L, cm, in.means3D, in.opacities,
+                     in.shs, in.colors_precomp, in.scales, in.rotations, in.cov3D_precomp, K1NoAdam{0});
 }
 
-void launch_preprocess_bwd(const ViewTab& tab, int nviews, const LOff& L, const Common& cm, const SgrInputs& in,
-                           const SgrGradInputs& g, const FusedAdam* fused, hipStream_t st, bool mapping_loop) {
-  if (L.N <= 0) return;
-  ProfScope prof(PK_PRE_BWD, st);
+static void launch_preprocess_bwd_dense(const ViewTab& tab, int nviews, const LOff& L, const Common& cm, const SgrInputs& in,
+                                        const SgrGradInputs& g, hipStream_t st, bool mapping_loop) {
   // Quad mode (four lanes per list entry) for the mapping loops' SINGLE-view iterations -- initialize_map's 1050 and final_refine's
   // thousands: one view's list is 300-500 waves at 64 entries per wave, less than half a wave per SIMD, and a young map's splats cover
   // hundreds to thousands of bins: the waves walk their long runs one Gaussian at a time.  A quarter of the entries per wave = four
@@ -1322,10 +1379,23 @@ void launch_preprocess_bwd(const ViewTab& tab, int nviews, const LOff& L, const 
   else
     hipLaunchKernelGGL(preprocess_bwd_dense_kernel<1>, dim3(L.pre_blocks, nviews), dim3(256), 0, st, tab, L, cm, in.means3D, in.shs,
                        in.colors_precomp, in.scales, in.rotations, in.cov3D_precomp, g.dL_dshs, g.dL_dcov3D_precomp, g.accumulate);
+}
+
+void launch_preprocess_bwd(const ViewTab& tab, int nviews, const LOff& L, const Common& cm, const SgrInputs& in,
+                           const SgrGradInputs& g, const FusedAdam* fused, hipStream_t st, bool mapping_loop, bool defer_adam) {
+  if (L.N <= 0) return;
   if (fused) {               // single-GPU mapping iteration: the gather rides in the optimiser pass (no gradient round trip)
+    {
+      ProfScope prof(PK_PRE_BWD, st);
+      launch_preprocess_bwd_dense(tab, nviews, L, cm, in, g, st, mapping_loop);
+    }
+    if (defer_adam) return;  // (sgr_map_run: the next iteration's K1 runs the pass, see preprocess_fwd_kernel<true>)
+    ProfScope prof(PK_PRE_BWD, st);       // a launch of its own, a record of its own
     launch_gather_adam(tab, nviews, L, *fused, st);
     return;
   }
+  ProfScope prof(PK_PRE_BWD, st);
+  launch_preprocess_bwd_dense(tab, nviews, L, cm, in, g, st, mapping_loop);
   hipLaunchKernelGGL(grad_gather_kernel, dim3(L.pre_blocks), dim3(256), 0, st, tab, nviews, L, cm.deg, cm.M,
                      in.colors_precomp != nullptr ? 1 : 0, g.dL_dmeans3D, g.dL_dmeans2D, g.dL_dopacities, g.dL_dshs,
                      g.dL_dcolors_precomp, g.dL_dscales, g.dL_drotations, g.dL_dcov3D_precomp, g.accumulate,
