@@ -30,7 +30,8 @@
  *                             neighbours, point-to-point ICP sums and the accuracy / completion reductions
  *   sgr_traj_*             -> src/utils/eval_traj.py: the camera centres and the skip rule of align_kf_traj (:20-55) and align_full_traj
  *                             (:57-80), the sums behind evo's PoseTrajectory3D.align(correct_scale=True) (umeyama_alignment), and the
- *                             errors and statistics of traj_eval_and_plot (:83-110: APE of the translation part, get_all_statistics)
+ *                             errors and statistics of traj_eval_and_plot (:83-110: APE of the translation part, get_all_statistics);
+ *                             sgr_traj_associate and sgr_traj_pose_errors: evo's time association and its APE / RPE of every pose relation
  *   sgr_plot_*             -> the per-keyframe figure of the same function (eval_utils.py:131-135, plot_rgbd_silhouette): the six cells,
  *                             their titles and the heading as one RGB panel
  *   sgr_frame_prepare      -> BaseDataset.__getitem__ / get_color of src/utils/datasets.py:133-216: cv2.undistort, cv2.resize, / 255, the
@@ -1391,6 +1392,48 @@ int sgr_traj_accumulate(int32_t kind, const float* est, int32_t est_rows, SGR_HO
                         double* pos, uint8_t* valid, double* sums, void* scratch, size_t scratch_bytes, void* stream);
 int sgr_traj_errors(int32_t n, const double* pos, const uint8_t* valid, SGR_HOST const double* sim3, double* err, double* stats,
                     void* scratch, size_t scratch_bytes, void* stream);
+
+/* Time association and pose-to-pose errors ("Trajectory scoring": evo's matching_time_indices, APE and RPE of
+ * every pose relation).  The same house rules: stream-ordered, no allocation, fp64, fixed-order reductions, bitwise reproducible.
+ * sgr_traj_associate (SGR_TRAJ_ASSOCIATE_LAUNCHES launches): for every stamps_a[i], i < na, the nearest of stamps_b[j] + offset_b,
+ *   j < nb (stamps_b non-decreasing): j = argmin_j |(stamps_b[j] + offset_b) - stamps_a[i]| in fp64 as written, the lowest j among
+ *   equal distances; match[i] = j where that distance <= max_diff, else -1 (a NaN distance is no match).  Several i may share a j.
+ *   1 <= na <= SGR_TRAJ_MAX_POSES, 1 <= nb <= SGR_TRAJ_MAX_STAMPS; scratch: sgr_traj_associate_scratch_bytes(na, nb) (0 = unsupported).
+ *   a_inds[na], b_inds[na]: the matched (i, match[i]) compacted in the order of i, -1 behind them.
+ *   header[SGR_TRAJ_HEADER_WORDS]: [0] the number of matches, [1] 1 iff some stamps_b[j + 1] >= stamps_b[j] does not hold (EVERY j is
+ *   looked at, a NaN stamp counts as out of order; match is then within bounds but meaningless), the rest 0.
+ * sgr_traj_pose_errors (SGR_TRAJ_POSE_ERRORS_LAUNCHES launches): pair i < n is (row est_inds[i] of est, row ref_inds[i] of ref), row i
+ *   of either where its DEVICE list is NULL.  est as in sgr_traj_accumulate, but a pose7 row is normalised and inverted in fp64;
+ *   ref [ref_rows, 16]; both 4 x 4 layouts 16-byte aligned, of each matrix the upper 3 x 4 [R | t] is used as a rigid pose.
+ *   A pair is unused iff an index is outside [0, rows), or any entry of its ref row or of its est row is not finite (nor its
+ *   normalised pose: a zero quaternion).  P = [r_a R | s r_a t + t_a] of the estimate under sim3 (as sgr_traj_errors), Q the reference.
+ *   The c used pairs are ranked in the order of i.  mode SGR_TRAJ_ABSOLUTE: one item per used pair, E = Q^-1 P.  SGR_TRAJ_RELATIVE,
+ *   delta >= 1: items over the ranks (k delta, (k + 1) delta), k < floor((c - 1) / delta), or with all_pairs (r, r + delta), r < c - delta;
+ *   E = (Q_i^-1 Q_j)^-1 (P_i^-1 P_j).  Inverses are rigid: [R | t]^-1 = [R^T | -R^T t].  The error of an item by `relation`:
+ *   |E_t|, atan2(|a|, tr E_R - 1) with a = (E32 - E23, E13 - E31, E21 - E12) in radians or degrees, |E_R - I|_F, |E - I|_F.
+ *   err[n]: the m items' errors, NaN behind them; pair_rows[n,2]: the pairs i (and j, else -1) of each item, -1 behind them;
+ *   stats[8] over the items, the layout and the device code of sgr_traj_errors; header: [0] m, [1] c, [2] n - c, [3] 0.
+ *   scratch: sgr_traj_pose_errors_scratch_bytes(n) (0 = unsupported n). */
+#define SGR_TRAJ_MAX_STAMPS 16777216
+#define SGR_TRAJ_HEADER_WORDS 4
+#define SGR_TRAJ_ASSOCIATE_LAUNCHES 2
+#define SGR_TRAJ_POSE_ERRORS_LAUNCHES 4
+#define SGR_TRAJ_ABSOLUTE 0
+#define SGR_TRAJ_RELATIVE 1
+#define SGR_TRAJ_TRANSLATION_PART 0
+#define SGR_TRAJ_ROTATION_ANGLE_RAD 1
+#define SGR_TRAJ_ROTATION_ANGLE_DEG 2
+#define SGR_TRAJ_ROTATION_PART 3
+#define SGR_TRAJ_FULL_TRANSFORMATION 4
+size_t sgr_traj_associate_scratch_bytes(int32_t na, int32_t nb);
+int sgr_traj_associate(const double* stamps_a, int32_t na, const double* stamps_b, int32_t nb, double offset_b, double max_diff,
+                       int32_t* match, int32_t* a_inds, int32_t* b_inds, int32_t* header, void* scratch, size_t scratch_bytes,
+                       void* stream);
+size_t sgr_traj_pose_errors_scratch_bytes(int32_t n);
+int sgr_traj_pose_errors(int32_t kind, const float* est, int32_t est_rows, const float* ref, int32_t ref_rows, const int32_t* est_inds,
+                         const int32_t* ref_inds, int32_t n, SGR_HOST const double* sim3, int32_t mode, int32_t delta, int32_t all_pairs,
+                         int32_t relation, double* err, int32_t* pair_rows, double* stats, int32_t* header, void* scratch,
+                         size_t scratch_bytes, void* stream);
 
 /* Frame preparation of the dataset streams (src/utils/datasets.py:170-216; DESIGN.md section 3, "Datasets and frame preparation"):
  * undistortion, bilinear resize to (H_oe, W_oe), crop of the edge and / 255 of the colour, nearest resize, crop and / depth_scale of the

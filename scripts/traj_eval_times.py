@@ -1,7 +1,7 @@
 """GPU box: times of the trajectory scoring (csrc/sgr_traj.hip, splat_slam_amd.traj_eval) at n = 512 keyframes and n = 2 000 frames:
 the two entry points (HIP events around a batch of calls on one stream: the per-call time with the launches back to back), one
 kf_traj_eval (host clock around work that ends in a device synchronise: two read-backs), and the obvious alternative, alternating
-with it in the same process: download video.poses, then the numpy fp64 restatement (centres, Umeyama, errors, statistics).  No claim
+with it in the same process: download video.poses, then the numpy fp64 restatement (centres, Umeyama, errors, statistics); the same for sgr_traj_associate, sgr_traj_pose_errors and one rpe().  No claim
 is made in advance: at these sizes both are dominated by fixed costs, and the file says what was measured.  Writes one JSON file.
 
     python scripts/traj_eval_times.py [--out profiles/traj_eval_times.json] [--reps 30] [--batch 200]"""
@@ -69,6 +69,68 @@ def numpy_kf_traj_eval(video, gt):
             "min": float(e.min()), "max": float(e.max()), "sse": float((e * e).sum())}, float(s)
 
 
+def numpy_rpe(video, gt, sim3, delta):
+    """the alternative to rpe(): one download of the poses, then the relative translation error in numpy fp64"""
+    n = video.counter.value
+    p = video.poses[:n].cpu().numpy().astype(np.float64)
+    ok = np.isfinite(gt.reshape(n, 16).sum(1))
+    s, r_a, t_a = sim3
+    q = p[:, 3:] / np.linalg.norm(p[:, 3:], axis=1, keepdims=True)
+    x, y, z, w = q.T
+    rot = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y + z * w), 2 * (x * z - y * w), 2 * (x * y - z * w), 1 - 2 * (x * x + z * z),
+                    2 * (y * z + x * w), 2 * (x * z + y * w), 2 * (y * z - x * w), 1 - 2 * (x * x + y * y)], -1).reshape(n, 3, 3)
+    P = np.tile(np.eye(4), (n, 1, 1))
+    P[:, :3, :3] = r_a @ rot
+    P[:, :3, 3] = s * np.einsum("ij,nj->ni", r_a, -np.einsum("nij,nj->ni", rot, p[:, :3])) + t_a
+    P, Q = P[ok], gt[ok].astype(np.float64)
+    i = np.arange(0, len(P) - delta, delta)[:(len(P) - 1) // delta]
+    E = np.linalg.inv(np.linalg.inv(Q[i]) @ Q[i + delta]) @ (np.linalg.inv(P[i]) @ P[i + delta])
+    e = np.linalg.norm(E[:, :3, 3], axis=1)
+    return {"rmse": float(np.sqrt((e * e).mean())), "mean": float(e.mean()), "median": float(np.median(e))}
+
+
+def pose_error_times(n, video, gt, ref, sim3, args, nat, te, lib, stream):
+    """sgr_traj_associate (n stamps into a clock five times as dense) and sgr_traj_pose_errors (relative, delta 1, translation part) per
+    call, and one rpe() against numpy_rpe(), alternating"""
+    rng = np.random.default_rng(n + 1)
+    stamps_b = torch.tensor(np.arange(5 * n) * 0.01, device=DEV)
+    stamps_a = torch.tensor(np.sort(rng.choice(5 * n, n, replace=False)) * 0.01 + rng.uniform(-0.002, 0.002, n), device=DEV)
+    out = torch.empty(3, n, dtype=torch.int32, device=DEV)
+    header = torch.empty(nat.SGR_TRAJ_HEADER_WORDS, dtype=torch.int32, device=DEV)
+    a_bytes = lib.sgr_traj_associate_scratch_bytes(n, 5 * n)
+    a_scratch = torch.empty(a_bytes, dtype=torch.uint8, device=DEV)
+    assoc = lambda: nat.check(lib.sgr_traj_associate(stamps_a.data_ptr(), n, stamps_b.data_ptr(), 5 * n, 0.0, 0.005, out[0].data_ptr(),
+                                                     out[1].data_ptr(), out[2].data_ptr(), header.data_ptr(), a_scratch.data_ptr(), a_bytes,
+                                                     stream), "associate")
+    s, r, t = sim3
+    c_sim3 = (nat.C.c_double * 13)(s, *r.reshape(-1).tolist(), *t.tolist())
+    p_bytes = lib.sgr_traj_pose_errors_scratch_bytes(n)
+    p_scratch = torch.empty(p_bytes, dtype=torch.uint8, device=DEV)
+    err = torch.empty(n, dtype=torch.float64, device=DEV)
+    pair_rows = torch.empty(n, 2, dtype=torch.int32, device=DEV)
+    stats = torch.empty(8, dtype=torch.float64, device=DEV)
+    flat = ref.reshape(n, 16)
+    pose = lambda: nat.check(lib.sgr_traj_pose_errors(te.POSE7_W2C, video.poses.data_ptr(), n, flat.data_ptr(), n, None, None, n, c_sim3,
+                                                      nat.SGR_TRAJ_RELATIVE, 1, 0, nat.SGR_TRAJ_TRANSLATION_PART, err.data_ptr(),
+                                                      pair_rows.data_ptr(), stats.data_ptr(), header.data_ptr(), p_scratch.data_ptr(), p_bytes,
+                                                      stream), "pose_errors")
+    row = {"sgr_traj_associate": batch_us(assoc, args.batch, args.reps), "sgr_traj_pose_errors": batch_us(pose, args.batch, args.reps)}
+    al = te.Alignment(r, t, s, 0, 0)
+    hip, alt = [], []
+    te.rpe(video.poses[:n], ref, al, delta=1)
+    numpy_rpe(video, gt, sim3, 1)
+    for _ in range(args.reps):                           # alternating, same process
+        us, got = host_us(lambda: te.rpe(video.poses[:n], ref, al, delta=1).stats)
+        hip.append(us)
+        us, want = host_us(lambda: numpy_rpe(video, gt, sim3, 1))
+        alt.append(us)
+    spread = lambda v: {"median_us": float(np.median(v)), "min_us": float(np.min(v)), "max_us": float(np.max(v))}
+    row["rpe_host_us"] = spread(hip)
+    row["numpy_rpe_after_download_host_us"] = spread(alt)
+    row["rpe_rmse"] = {"hip": got["rmse"], "numpy": want["rmse"]}
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "traj_eval_times.json"))
@@ -81,7 +143,7 @@ def main():
     from splat_slam_amd.depth_video import DepthVideo
     lib = nat.lib()
     stream = torch.cuda.current_stream().cuda_stream
-    out = dict(device=torch.cuda.get_device_name(0), reps=args.reps, batch=args.batch, launches=te.LAUNCHES, sizes={})
+    out = dict(device=torch.cuda.get_device_name(0), reps=args.reps, batch=args.batch, launches={**te.LAUNCHES, **te.POSE_LAUNCHES}, sizes={})
     for n in (512, 2000):
         rng = np.random.default_rng(n)
         x = np.cumsum(rng.normal(scale=0.02, size=(n, 3)), 0)
@@ -105,6 +167,7 @@ def main():
         errs = lambda: nat.check(lib.sgr_traj_errors(n, pairs.pos.data_ptr(), pairs.valid.data_ptr(), sim3, err.data_ptr(), stats.data_ptr(),
                                                      scratch.data_ptr(), nbytes, stream), "err")
         row = {"sgr_traj_accumulate": batch_us(acc, args.batch, args.reps), "sgr_traj_errors": batch_us(errs, args.batch, args.reps)}
+        row.update(pose_error_times(n, video, gt, ref, (s, r, t), args, nat, te, lib, stream))
         hip, alt = [], []
         te.kf_traj_eval(video, gt)
         numpy_kf_traj_eval(video, gt)

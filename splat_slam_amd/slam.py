@@ -20,7 +20,7 @@ the result goes to session.process -- or, with fewer than 100 valid tracker pixe
 one batched fusion call (the pose source's prefetch).  The mono-depth network is splat_slam_amd.mono_depth.MonoDepth, itself such a callable.
 
     slam.evaluate(gt_poses=None, gt_depths=None, mesh=False, gt_mesh_path=None, lpips=None, out_dir=None, cull_mesh=False,
-                  plots=False) -> dict
+                  plots=False, rpe_delta=None, rotation_errors=False) -> dict
         after terminate(): the rest of the reference's terminate() (slam.py:169-242) in its order, on splat_slam_amd.traj_eval.
         gt_poses: camera -> world 4x4 per frame of the stream, indexed by timestamp (default stream.poses when the stream has one).
         "kf_traj": the ATE statistics of the keyframes after the scaled Umeyama alignment (kf_traj_eval), "global_scale", "r_a", "t_a":
@@ -39,6 +39,9 @@ one batched fusion call (the pose source's prefetch).  The mono-depth network is
         plots=True (needs out_dir, ValueError otherwise): the two trajectory evaluations also write kf_traj.png and full_traj.png, and after
         eval_rendering, splat_slam_amd.plots.plot_rendering writes plots_after_refine/video_idx_{V}_kf_idx_{T}.png per mapped viewpoint (T
         the keyframe's timestamp as an integer) and output.gif from that result.  The returned dict is the same.  Nothing is drawn by default.
+        rpe_delta=N: "kf_rpe" and "full_rpe", the statistics of the relative translation error over N used poses after the alignment
+        (traj_eval.pose_errors); rotation_errors=True: "kf_rot" and "full_rot", those of the absolute rotation angle in degrees.  Each is
+        None where its trajectory evaluation failed or left no item; none of the four keys exists unless asked for.
 
 `stream` for a Replica, ScanNet or TUM RGB-D folder: splat_slam_amd.datasets.get_dataset(splat_slam_amd.config.load_config(...)).
 The command line and the output tree: splat_slam_amd.run.  Not provided: a mode without a mapper (--only_tracking),
@@ -125,16 +128,28 @@ class Slam:
         return self.session.finish()
 
     def evaluate(self, gt_poses=None, gt_depths=None, mesh=False, gt_mesh_path=None, lpips=None, out_dir=None, cull_mesh=False,
-                 plots=False):
+                 plots=False, rpe_delta=None, rotation_errors=False):
         from splat_slam_amd import traj_eval
         from splat_slam_amd.trajectory_filler import PoseTrajectoryFiller
         if plots and out_dir is None:
             raise ValueError("Slam.evaluate(plots=True) needs out_dir: the figures are files")
         plot = {"plot": True} if plots else {}
+        extra = ([("translation_part", int(rpe_delta), False)] if rpe_delta is not None else []) + \
+            ([("rotation_angle_deg", None, False)] if rotation_errors else [])
+        if extra:
+            plot = dict(plot, extra=extra)
+
+        def more(prefix, results):                     # the entries of `extra` under their keys of the returned dict
+            if rpe_delta is not None:
+                out[prefix + "_rpe"] = results.get(traj_eval.extra_key(*extra[0]))
+            if rotation_errors:
+                out[prefix + "_rot"] = results.get(traj_eval.extra_key(*extra[-1]))
         if gt_poses is None:
             gt_poses = getattr(self.stream, "poses", None)
         out = {"kf_traj": None, "global_scale": 1.0, "r_a": None, "t_a": None, "rendering": None, "depth_l1": None, "full_traj": None,
                "full_traj_alignment": None, "traj_est": None}
+        more("kf", {})
+        more("full", {})
         npz = None
         if out_dir is not None:
             os.makedirs(out_dir, exist_ok=True)
@@ -143,7 +158,8 @@ class Slam:
         alignment = None
         if gt_poses is not None:
             try:
-                out["kf_traj"], s, r_a, t_a = traj_eval.kf_traj_eval(self.video, gt_poses, out_dir=out_dir, npz_path=npz, **plot)
+                out["kf_traj"], s, r_a, t_a, *rest = traj_eval.kf_traj_eval(self.video, gt_poses, out_dir=out_dir, npz_path=npz, **plot)
+                more("kf", rest[0] if rest else {})
                 alignment = traj_eval.Alignment(r_a, t_a, s, 0, 0)
                 out["global_scale"], out["r_a"], out["t_a"] = s, r_a, t_a
             except traj_eval.TrajectoryDegenerate as e:
@@ -173,8 +189,9 @@ class Slam:
             out["depth_l1"] = self._depth_l1(out["global_scale"], npz)
         if gt_poses is not None:
             try:
-                out["traj_est"], out["full_traj"], out["full_traj_alignment"] = traj_eval.full_traj_eval(
+                out["traj_est"], out["full_traj"], out["full_traj_alignment"], *rest = traj_eval.full_traj_eval(
                     PoseTrajectoryFiller(self.net, self.video, device=self.video.device), self.stream, gt_poses, out_dir=out_dir, **plot)
+                more("full", rest[0] if rest else {})
             except traj_eval.TrajectoryDegenerate as e:
                 out["full_traj_error"] = str(e)
         return out
