@@ -1498,6 +1498,26 @@ size_t sgr_plot_scratch_bytes(int32_t n);
 int sgr_plot_panels(int32_t n, const SgrPlotFrame* frames, int32_t H, int32_t W, int32_t s, float global_scale, float depth_max,
                     uint8_t* panels, void* scratch, size_t scratch_bytes, void* stream);
 
+/* Exposure fit of the novel-view evaluation ("Novel-view evaluation"; the reference scores mapped keyframes only
+ * and has no counterpart).  For each of 1 <= n <= SGR_EXPOSURE_FIT_MAX_FRAMES rows of the host table `frames`, of which render and
+ * gt_image [C,H,W] are read and the other fields ignored, the gain g and bias b that minimise
+ *   sum over the elements with gt_image > 0 of (g render + b - gt_image)^2        (the mask of sgr_render_metrics' PSNR)
+ * from the six fp64 sums m (the mask count), S_r, S_t, S_rr, S_rt, S_tt (r = render, t = gt_image; every term formed in fp64):
+ *   det = m S_rr - S_r^2,   g = (m S_rt - S_r S_t) / det,   b = (S_t - g S_r) / m;   ab[2 f] = log g, ab[2 f + 1] = b.
+ * flags[f] = 1 and ab[2 f] = ab[2 f + 1] = 0 (the identity) where m < 2, or det <= 0 or det is not above m^2 2^-40 max(S_rr / m, 1)
+ * (a render that is constant on the mask), or g is <= 0 or not finite, or a value would not be finite as fp32; else flags[f] = 0.
+ * Nothing that is not finite is written.  A caller points exposure_a / exposure_b of row f at ab + 2 f and ab + 2 f + 1 and hands the
+ * same table to sgr_render_metrics, sgr_lpips_pack and sgr_plot_panels behind this call on the same stream.
+ * SGR_EXPOSURE_FIT_LAUNCHES launches, stream-ordered, no allocation, no float atomics; the order of every addition is fixed (per lane,
+ * across the wave, the waves left to right, then the workgroups in order), so a frame's result has the same bits alone and in any
+ * batch.  scratch: sgr_exposure_fit_bytes(n, C, H, W) (0 = unsupported: n outside its range, a side < 1 or C H W > 2^30).
+ * SGR_ERR_INVALID / SGR_ERR_WORKSPACE before anything is launched. */
+#define SGR_EXPOSURE_FIT_MAX_FRAMES 16
+#define SGR_EXPOSURE_FIT_LAUNCHES 2
+size_t sgr_exposure_fit_bytes(int32_t n, int32_t C, int32_t H, int32_t W);
+int sgr_exposure_fit(int32_t n, const SgrMetricFrame* frames, int32_t C, int32_t H, int32_t W, float* ab, int32_t* flags, void* scratch,
+                     size_t scratch_bytes, void* stream);
+
 /* SE3 ops, batched over n. Pose =(tx,ty,tz,qx,qy,qz,qw) as in lietorch / depth_video.py:69; tau = (rho, theta). */
 int se3_exp(const float* tau, int64_t n, float* pose_out, void* stream);
 int se3_log(const float* pose, int64_t n, float* tau_out, void* stream);

@@ -1,8 +1,8 @@
 """A whole run from a config file (the reference's run.py and SLAM.__init__ / terminate, in their order; DESIGN.md section 3, "Run"):
 
-    python -m splat_slam_amd.run CONFIG [--default PATH] [--root DIR] [--lpips-weights PATH]
+    python -m splat_slam_amd.run CONFIG [--default PATH] [--root DIR] [--lpips-weights PATH] [--novel_views N]
 
-    run(cfg, net=None, mono_depth=None, lpips=None, stream=None) -> dict       what main calls; the result of Slam.evaluate with
+    run(cfg, net=None, mono_depth=None, lpips=None, stream=None, novel_views=None) -> dict       what main calls; the result of Slam.evaluate with
         "output_dir", "psnr" (terminate()'s list) and "num_gaussians" (the rows of the written map) added.  Objects that are not given are
         built from the config: the stream by datasets.get_dataset(cfg), net by load_droid_net(cfg["tracking"]["pretrained"]), mono_depth
         by load_mono_depth(cfg["mono_prior"]["depth_pretrained"]).
@@ -15,7 +15,9 @@
 The output tree under cfg["data"]["output"]/cfg["scene"]: cfg.yaml, video.npz, metrics_kf_traj.txt, metrics_full_traj.txt, kf_traj.png,
 full_traj.png, plots_after_refine/ (one PNG per mapped keyframe and output.gif), mesh.ply with meshing.mesh,
 psnr/after_refine/final_result.json (mean_psnr, mean_ssim, mean_depthl1 and, with LPIPS weights, mean_lpips), depth_stats.txt (the
-reference's nine labels, slam.py:220-235) and point_cloud/final/point_cloud.ply.  Progress and results go to the logger
+reference's nine labels, slam.py:220-235) and point_cloud/final/point_cloud.ply.  With --novel_views N also
+psnr/novel_views/final_result.json: the same means over every N-th frame that is no keyframe (splat_slam_amd.novel_view, exposure fitted
+per frame), with the frames scored and the number of degenerate fits; without the flag the tree is unchanged.  Progress and results go to the logger
 "splat_slam_amd.run"; there is no print process.
 
 Not provided, each refused with NotImplementedError before anything is loaded: only_tracking (Slam has no mode without a mapper),
@@ -82,6 +84,15 @@ def _write_results(out_dir, result):
         with open(path, "w", encoding="utf-8") as f:
             json.dump(final, f, indent=4)
         log.info("rendering: %s", final)
+    novel = result.get("novel_views")
+    if novel is not None:
+        final = {k: novel[k] for k in ("mean_psnr", "mean_ssim", "mean_lpips", "mean_depthl1") if k in novel}
+        final.update(frame_ids=novel["frame_ids"], exposure="fit", degenerate_fits=int(sum(novel["exposure_flags"])))
+        path = os.path.join(out_dir, "psnr", "novel_views", "final_result.json")
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w", encoding="utf-8") as f:
+            json.dump(final, f, indent=4)
+        log.info("novel views: %s", {k: v for k, v in final.items() if k != "frame_ids"})
     d = result["depth_l1"] or {}
     values = (d.get("depth_l1"), d.get("depth_l1_global_scale"), d.get("depth_l1_mask_4m"), d.get("depth_l1_mask_4m_global_scale"),
               d.get("coverage"), result["global_scale"], result["r_a"], result["t_a"], result["kf_traj"])
@@ -91,10 +102,12 @@ def _write_results(out_dir, result):
     log.info("keyframe trajectory: %s; sensor depth: %s", result["kf_traj"], result["depth_l1"])
 
 
-def run(cfg, net=None, mono_depth=None, lpips=None, stream=None):
+def run(cfg, net=None, mono_depth=None, lpips=None, stream=None, novel_views=None):
     from splat_slam_amd.fused import FusedMappingLoop
     from splat_slam_amd.slam import Slam
     check_supported(cfg)
+    if novel_views is not None and int(novel_views) < 1:
+        raise ValueError(f"novel_views={novel_views}: every N-th frame, N >= 1")
     setup_seed(cfg["setup_seed"])
     out_dir = os.path.join(cfg["data"]["output"], str(cfg["scene"]))
     os.makedirs(out_dir, exist_ok=True)
@@ -119,7 +132,7 @@ def run(cfg, net=None, mono_depth=None, lpips=None, stream=None):
         psnr = slam.terminate()
         meshing = cfg.get("meshing", {})
         result = slam.evaluate(out_dir=out_dir, mesh=bool(meshing.get("mesh", False)), gt_mesh_path=meshing.get("gt_mesh_path") or None,
-                               lpips=lpips, plots=True)
+                               lpips=lpips, plots=True, **({} if novel_views is None else {"novel_views": int(novel_views)}))
         _write_results(out_dir, result)
         result["num_gaussians"] = 0
         if not slam.session.init:
@@ -141,12 +154,16 @@ def main(argv=None):
                         "configs/splat_slam.yaml)")
     parser.add_argument("--root", type=str, default=None, help="directory that relative inherit_from paths are resolved against")
     parser.add_argument("--lpips-weights", type=str, default=None, help="an LPIPS (AlexNet) state dict; without it LPIPS is not reported")
+    parser.add_argument("--novel_views", type=int, default=None, metavar="N", help="also score every N-th frame that is no keyframe "
+                        "(psnr/novel_views/final_result.json); without it only the mapped keyframes are scored")
     args = parser.parse_args(argv)
+    if args.novel_views is not None and args.novel_views < 1:
+        parser.error("--novel_views N: every N-th frame, N >= 1")
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(name)s: %(message)s")
     cfg = config_mod.load_config(args.config, args.default, args.root)
     check_supported(cfg)
     lpips = load_lpips(args.lpips_weights) if args.lpips_weights else None
-    result = run(cfg, lpips=lpips)
+    result = run(cfg, lpips=lpips, **({} if args.novel_views is None else {"novel_views": args.novel_views}))
     return 0 if result is not None else 1
 
 

@@ -208,3 +208,11 @@ class MappingSession:
         return eval_rendering(frames, self.loop.gaussians, PipelineParams(), self.loop.background, gt_depths=gt_depths,
                               global_scale=global_scale, mesh=mesh, mesh_path=mesh_path, gt_mesh_path=gt_mesh_path,
                               distance_thresh=distance_thresh, icp_align=icp_align, mesh_samples=mesh_samples, lpips=lpips)
+
+    def evaluate_novel_views(self, stream, c2w, frame_ids, exposure="fit", global_scale=1.0, lpips=None, kf_timestamps=None):
+        """The same metrics at frames of the stream that are no keyframes (splat_slam_amd.novel_view.eval_novel_views): c2w [T,4,4] the
+        camera -> world pose of every frame in the map's frame, frame_ids the frames to score (novel_view.select_frames), exposure
+        "fit" (per frame, sgr_exposure_fit), "keyframes" (interpolated between the mapped keyframes') or "none"."""
+        from splat_slam_amd.novel_view import eval_novel_views
+        return eval_novel_views(self, stream, c2w, frame_ids, exposure=exposure, global_scale=global_scale, lpips=lpips,
+                                kf_timestamps=kf_timestamps)

@@ -20,7 +20,7 @@ the result goes to session.process -- or, with fewer than 100 valid tracker pixe
 one batched fusion call (the pose source's prefetch).  The mono-depth network is splat_slam_amd.mono_depth.MonoDepth, itself such a callable.
 
     slam.evaluate(gt_poses=None, gt_depths=None, mesh=False, gt_mesh_path=None, lpips=None, out_dir=None, cull_mesh=False,
-                  plots=False, rpe_delta=None, rotation_errors=False) -> dict
+                  plots=False, rpe_delta=None, rotation_errors=False, novel_views=None, novel_exposure="fit") -> dict
         after terminate(): the rest of the reference's terminate() (slam.py:169-242) in its order, on splat_slam_amd.traj_eval.
         gt_poses: camera -> world 4x4 per frame of the stream, indexed by timestamp (default stream.poses when the stream has one).
         "kf_traj": the ATE statistics of the keyframes after the scaled Umeyama alignment (kf_traj_eval), "global_scale", "r_a", "t_a":
@@ -42,6 +42,10 @@ one batched fusion call (the pose source's prefetch).  The mono-depth network is
         rpe_delta=N: "kf_rpe" and "full_rpe", the statistics of the relative translation error over N used poses after the alignment
         (traj_eval.pose_errors); rotation_errors=True: "kf_rot" and "full_rot", those of the absolute rotation angle in degrees.  Each is
         None where its trajectory evaluation failed or left no item; none of the four keys exists unless asked for.
+        novel_views=N: "novel_views", splat_slam_amd.novel_view.eval_novel_views over every N-th frame of the stream that is no keyframe
+        of the video (select_frames: neither a warm-up keyframe nor one the session registered, mapped or not), at its pose of the filled trajectory (computed once, shared with full_traj_eval; without ground-truth
+        poses it is computed for this alone), with global_scale, lpips and the exposure mode novel_exposure ("fit", "keyframes" or
+        "none").  None without a map or when every such frame is a keyframe; the key does not exist unless asked for.
 
 `stream` for a Replica, ScanNet or TUM RGB-D folder: splat_slam_amd.datasets.get_dataset(splat_slam_amd.config.load_config(...)).
 The command line and the output tree: splat_slam_amd.run.  Not provided: a mode without a mapper (--only_tracking),
@@ -128,7 +132,7 @@ class Slam:
         return self.session.finish()
 
     def evaluate(self, gt_poses=None, gt_depths=None, mesh=False, gt_mesh_path=None, lpips=None, out_dir=None, cull_mesh=False,
-                 plots=False, rpe_delta=None, rotation_errors=False):
+                 plots=False, rpe_delta=None, rotation_errors=False, novel_views=None, novel_exposure="fit"):
         from splat_slam_amd import traj_eval
         from splat_slam_amd.trajectory_filler import PoseTrajectoryFiller
         if plots and out_dir is None:
@@ -150,6 +154,15 @@ class Slam:
                "full_traj_alignment": None, "traj_est": None}
         more("kf", {})
         more("full", {})
+        novel_ids = []
+        if novel_views is not None:
+            from splat_slam_amd.novel_view import EXPOSURE_MODES, select_frames
+            if novel_exposure not in EXPOSURE_MODES:
+                raise ValueError(f"Slam.evaluate: novel_exposure={novel_exposure!r}, one of {EXPOSURE_MODES}")
+            out["novel_views"] = None
+            if not self.session.init:              # the video's keyframes: the warm-up ones and every one the session registered
+                stamps = self.video.timestamp[:self.video.counter.value].cpu().tolist()
+                novel_ids = select_frames(len(self.stream), stamps, every=novel_views)
         npz = None
         if out_dir is not None:
             os.makedirs(out_dir, exist_ok=True)
@@ -187,13 +200,21 @@ class Slam:
                                os.path.join(out_dir, "plots_after_refine"), names, gt_depths=gt_depths, global_scale=out["global_scale"])
         if self.video.counter.value > 0 and hasattr(self.stream, "__getitem__") and self.stream[0][2] is not None:
             out["depth_l1"] = self._depth_l1(out["global_scale"], npz)
+        filler = lambda: PoseTrajectoryFiller(self.net, self.video, device=self.video.device)
+        traj = traj_eval.filled_trajectory(filler(), self.stream) if novel_ids else None      # once: full_traj_eval scores the same rows
         if gt_poses is not None:
             try:
                 out["traj_est"], out["full_traj"], out["full_traj_alignment"], *rest = traj_eval.full_traj_eval(
-                    PoseTrajectoryFiller(self.net, self.video, device=self.video.device), self.stream, gt_poses, out_dir=out_dir, **plot)
+                    filler() if traj is None else None, self.stream, gt_poses, out_dir=out_dir, traj=traj, **plot)
                 more("full", rest[0] if rest else {})
             except traj_eval.TrajectoryDegenerate as e:
                 out["full_traj_error"] = str(e)
+        if novel_ids:
+            import lietorch
+            from splat_slam_amd.novel_view import eval_novel_views
+            c2w = out["traj_est"] if out["traj_est"] is not None else lietorch.SE3(traj).inv().matrix()
+            out["novel_views"] = eval_novel_views(self.session, self.stream, c2w, novel_ids, exposure=novel_exposure,
+                                                  global_scale=out["global_scale"], lpips=lpips)
         return out
 
     def _depth_l1(self, global_scale, npz):

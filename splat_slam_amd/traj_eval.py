@@ -16,6 +16,7 @@ conventions assumed about it.  No plots (evo.tools.plot has no counterpart here)
     kf_traj_eval(video, gt_poses, out_dir=None, npz_path=None, plot=False) -> (stats, s, r_a, t_a)         eval_traj.py:113-140
     full_traj_eval(filler, stream, gt_poses, out_dir=None, plot=False) -> (traj_unaligned [T,4,4], stats, alignment)     eval_traj.py:143-175
         plot=True with an out_dir also writes kf_traj.png / full_traj.png beside the metrics file; the return values are the same.
+    filled_trajectory(filler, stream) -> [T,7] world -> camera: what full_traj_eval scores (its `traj` keyword takes it back)
     aligned_c2w(cameras_or_c2w, alignment) -> [K,4,4] fp64       slam.py:145-152: PosePath3D.scale(s), then .transform(se3(r_a, t_a))
 
     associate(stamps_est, stamps_ref, max_diff=0.01, offset=0.0) -> Association(est_inds, ref_inds, n_matched)
@@ -51,7 +52,7 @@ RELATIONS = {"translation_part": nat.SGR_TRAJ_TRANSLATION_PART, "rotation_angle_
              "full_transformation": nat.SGR_TRAJ_FULL_TRANSFORMATION}
 
 __all__ = ["TrajectoryDegenerate", "Alignment", "Pairs", "umeyama", "pair_centres", "align", "ape", "ape_statistics", "aligned_c2w",
-           "kf_traj_eval", "full_traj_eval", "POSE7_W2C", "MAT4_C2W", "Association", "associate", "PoseErrors", "pose_errors", "rpe",
+           "kf_traj_eval", "full_traj_eval", "filled_trajectory", "POSE7_W2C", "MAT4_C2W", "Association", "associate", "PoseErrors", "pose_errors", "rpe",
            "ape_pose", "item_pairs", "read_tum_trajectory", "write_tum_trajectory", "evaluate_files", "main", "RELATIONS"]
 
 
@@ -484,18 +485,28 @@ def kf_traj_eval(video, gt_poses, out_dir=None, npz_path=None, plot=False, extra
 
 
 @torch.no_grad()
-def full_traj_eval(filler, stream, gt_poses, out_dir=None, plot=False, extra=None):
-    """Every frame of the stream: the filler's poses with the keyframes' rows overwritten by the video's (a device index copy, as
-    eval_traj.py:148-151 does on the host), aligned to gt_poses[i] and scored.  Returns the unaligned camera -> world trajectory
+def filled_trajectory(filler, stream):
+    """Every frame of the stream as a world -> camera pose7 row [T,7] (device): the filler's poses with the keyframes' rows overwritten
+    by the video's (a device index copy, as eval_traj.py:148-151 does on the host).  What full_traj_eval scores and, as
+    lietorch.SE3(.).inv().matrix(), returns; the novel-view evaluation needs it without ground-truth poses too."""
+    traj = filler(stream).contiguous()
+    video = filler.video
+    n = int(video.counter.value)
+    traj.index_copy_(0, video.timestamp[:n].long(), video.poses[:n])
+    return traj
+
+
+def full_traj_eval(filler, stream, gt_poses, out_dir=None, plot=False, extra=None, traj=None):
+    """Every frame of the stream: filled_trajectory(filler, stream) (or `traj`, that very result computed by the caller), aligned to
+    gt_poses[i] and scored.  Returns the unaligned camera -> world trajectory
     [T,4,4] (device), the statistics and the Alignment; with out_dir, metrics_full_traj.txt is written there.  extra: as kf_traj_eval
     (a fourth element)."""
     import lietorch
-    traj = filler(stream).contiguous()
-    video = filler.video
-    n, T = int(video.counter.value), int(traj.shape[0])
+    if traj is None:
+        traj = filled_trajectory(filler, stream)
+    T = int(traj.shape[0])
     if len(gt_poses) != T:
         raise ValueError(f"full_traj_eval: {len(gt_poses)} ground-truth poses for {T} frames")
-    traj.index_copy_(0, video.timestamp[:n].long(), video.poses[:n])
     ref = _gt_rows(gt_poses, range(T), traj.device)
     alignment = align(traj, ref, POSE7_W2C)
     stats = ape(alignment)
