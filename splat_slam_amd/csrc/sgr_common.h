@@ -146,6 +146,9 @@ struct SavedHeader {
 static_assert(sizeof(SavedHeader) == 64, "the header is one 64-byte record (sgr_query_header copies 16 words)");
 
 inline __host__ __device__ size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+// workgroups of `per` items that cover n items: 0 for n == 0.  A grid needs at least one, so a call site that launches on an empty
+// input says so itself (std::max(1, blocks_for(n))) or skips the launch.
+inline int blocks_for(long long n, int per = 256) { return (int)((n + per - 1) / per); }
 
 // ---- batched launches: every kernel takes the per-view pointers of up to kMaxViews views BY VALUE (kernarg) and picks
 // its view with blockIdx.y, so the <= 12 views of a mapping iteration (src/mapper.py:426-485) are ONE launch per stage.
@@ -471,18 +474,7 @@ __device__ __forceinline__ int wave_max_i32(int v) {
   for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
   return v;
 }
-// exclusive prefix of `v` inside a 256-thread block (4 waves) + block total; `red` = 4 uints of LDS
-__device__ __forceinline__ uint32_t block256_exclusive_scan(uint32_t v, uint32_t* red, uint32_t& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t inc = wave_scan_add_u32(v);
-  if (lane == 63) red[wv] = inc;
-  __syncthreads();
-  uint32_t w0 = red[0], w1 = red[1], w2 = red[2], w3 = red[3];
-  __syncthreads();
-  total = w0 + w1 + w2 + w3;
-  uint32_t base = (wv > 0 ? w0 : 0u) + (wv > 1 ? w1 : 0u) + (wv > 2 ? w2 : 0u);
-  return base + inc - v;
-}
+// (workgroup and device-wide scans on top of it: sgr_scan.h)
 
 // value of lane-1 (lane 0 receives `fill`)
 __device__ __forceinline__ float wave_shr1(float v, float fill) { return dpp_f<DPP_WAVE_SHR1>(fill, v); }

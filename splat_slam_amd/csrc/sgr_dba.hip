@@ -32,8 +32,6 @@ constexpr int kNb = 64;                     // Cholesky block
 constexpr int kHs = 4 * 36 + 12;            // per edge: Hii, Hij, Hji, Hjj (6x6 each), vi, vj
 constexpr int kStatusBadK = 1;              // number of distinct depth frames differs from eta.shape[0]
 
-inline int blocks(long long n) { return (int)((n + kThreads - 1) / kThreads); }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ---- SE3 on (t, q xyzw), fp32 as in the reference (act_so3, act_se3, rel_se3: sgr_dba_device.h)
 // Y = Adj(T)^T X for a 6-vector (translation part first)
@@ -843,7 +841,7 @@ size_t carve(int nv, int E, int K, int T, int P, char* base, DbaScratch* s) {
   size_t off = 0;
   auto take = [&](size_t bytes) {
     char* p = base ? base + off : nullptr;
-    off += align256(bytes);
+    off += align_up(bytes);
     return p;
   };
   const size_t f4 = sizeof(float), i4 = sizeof(int), n6 = 6 * (size_t)T;
@@ -916,16 +914,16 @@ int sgr_dba_ba(const SgrDbaProblem* pr, void* scratch, size_t scratch_bytes, voi
   hipStream_t st = (hipStream_t)stream;
   const int n = 6 * T, nbk = (n + kNb - 1) / kNb;
 
-  hipLaunchKernelGGL(mark_kernel, dim3(blocks(nv)), dim3(kThreads), 0, st, nv, E, pr->ii, pr->jj, t0, t1, s.flag, s.cnt_ii, s.cnt_jj);
+  hipLaunchKernelGGL(mark_kernel, dim3(blocks_for(nv)), dim3(kThreads), 0, st, nv, E, pr->ii, pr->jj, t0, t1, s.flag, s.cnt_ii, s.cnt_jj);
   hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, st, nv, K, motion_only ? 0 : 1, s.flag, s.rank, s.kx, s.cnt_ii, s.ptr_ii,
                      s.cnt_jj, s.ptr_jj, s.status);
-  hipLaunchKernelGGL(fill_kernel, dim3(blocks(nv)), dim3(kThreads), 0, st, nv, E, pr->ii, pr->jj, s.ptr_ii, s.idx_ii, s.ptr_jj, s.idx_jj);
+  hipLaunchKernelGGL(fill_kernel, dim3(blocks_for(nv)), dim3(kThreads), 0, st, nv, E, pr->ii, pr->jj, s.ptr_ii, s.idx_ii, s.ptr_jj, s.idx_jj);
   if (!motion_only) {
-    hipLaunchKernelGGL(slot_kernel, dim3(blocks((long long)K * T)), dim3(kThreads), 0, st, K, T, t0, pr->jj, s.kx, s.ptr_ii, s.idx_ii,
+    hipLaunchKernelGGL(slot_kernel, dim3(blocks_for((long long)K * T)), dim3(kThreads), 0, st, K, T, t0, pr->jj, s.kx, s.ptr_ii, s.idx_ii,
                        s.status, s.slot);
-    hipLaunchKernelGGL(klist_kernel, dim3(blocks(K)), dim3(kThreads), 0, st, K, T, s.slot, s.status, s.kcnt, s.kpose, s.kslot);
+    hipLaunchKernelGGL(klist_kernel, dim3(blocks_for(K)), dim3(kThreads), 0, st, K, T, s.slot, s.status, s.kcnt, s.kpose, s.kslot);
   }
-  const dim3 pix(blocks(P));
+  const dim3 pix(blocks_for(P));
   for (int it = 0; it < pr->iterations; ++it) {
     hipLaunchKernelGGL(linearize_kernel, dim3(E), dim3(kThreads), 0, st, nv, P, wd, pr->targets, pr->weights, pr->poses, pr->disps,
                        pr->intrinsics, pr->ii, pr->jj, s.status, s.Hs, s.Eii, s.Eij, s.Cii, s.bz);
@@ -973,7 +971,7 @@ int sgr_dba_projmap(const float* poses, int32_t num_poses, const float* disps, i
   if (!poses || !disps || !intrinsics || !ii || !jj || !coords || !valid || num_edges < 0 || num_edges > 65535 || ht <= 0 || wd <= 0)
     return set_error(SGR_ERR_INVALID, "dba_projmap: bad arguments");
   if (num_edges == 0) return SGR_OK;
-  hipLaunchKernelGGL(projmap_kernel, dim3(blocks(ht * wd), num_edges), dim3(kThreads), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(projmap_kernel, dim3(blocks_for(ht * wd), num_edges), dim3(kThreads), 0, (hipStream_t)stream,
                      std::min(num_poses, num_frames), ht * wd, wd, poses, disps, intrinsics, ii, jj, coords, valid);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "dba_projmap launch failed");
 }
@@ -983,7 +981,7 @@ int sgr_dba_iproj(const float* poses, const float* disps, int32_t num_frames, in
   if (!poses || !disps || !intrinsics || !points || num_frames < 0 || num_frames > 65535 || ht <= 0 || wd <= 0)
     return set_error(SGR_ERR_INVALID, "dba_iproj: bad arguments");
   if (num_frames == 0) return SGR_OK;
-  hipLaunchKernelGGL(iproj_kernel, dim3(blocks(ht * wd), num_frames), dim3(kThreads), 0, (hipStream_t)stream, ht * wd, wd, poses, disps,
+  hipLaunchKernelGGL(iproj_kernel, dim3(blocks_for(ht * wd), num_frames), dim3(kThreads), 0, (hipStream_t)stream, ht * wd, wd, poses, disps,
                      intrinsics, points);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "dba_iproj launch failed");
 }
@@ -993,7 +991,7 @@ int sgr_dba_depth_filter(const float* poses, const float* disps, int32_t num_fra
   if (!poses || !disps || !intrinsics || !inds || !thresh || !counter || num < 0 || num > 65535 || ht <= 0 || wd <= 0)
     return set_error(SGR_ERR_INVALID, "dba_depth_filter: bad arguments");
   if (num == 0) return SGR_OK;
-  hipLaunchKernelGGL(depth_filter_kernel, dim3(blocks(ht * wd), num), dim3(kThreads), 0, (hipStream_t)stream, num_frames, ht, wd, poses,
+  hipLaunchKernelGGL(depth_filter_kernel, dim3(blocks_for(ht * wd), num), dim3(kThreads), 0, (hipStream_t)stream, num_frames, ht, wd, poses,
                      disps, intrinsics, inds, thresh, counter);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "dba_depth_filter launch failed");
 }

@@ -30,8 +30,6 @@ constexpr float kValidGain = 10.f;          // weight of the prior on pixels of 
 constexpr int kSums = 7;                    // per-frame sums of the reduced 2 x 2 system (see system_kernel)
 constexpr int kStatusBadM = 1;              // number of distinct depth frames differs from eta.shape[0]
 
-inline int blocks(long long n) { return (int)((n + kThreads - 1) / kThreads); }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
@@ -337,7 +335,7 @@ size_t carve(int nv, int E, int M, int P, char* base, DspoScratch* s) {
   size_t off = 0;
   auto take = [&](size_t bytes) {
     char* p = base ? base + off : nullptr;
-    off += align256(bytes);
+    off += align_up(bytes);
     return p;
   };
   const size_t i4 = sizeof(int);
@@ -350,7 +348,7 @@ size_t carve(int nv, int E, int M, int P, char* base, DspoScratch* s) {
   d.status = (int*)take(i4);
   d.edges = (EdgePose*)take((size_t)E * sizeof(EdgePose));
   d.QB = (float*)take((size_t)M * 3 * P * sizeof(float));
-  d.partial = (double*)take((size_t)M * blocks(P) * kSums * sizeof(double));
+  d.partial = (double*)take((size_t)M * blocks_for(P) * kSums * sizeof(double));
   if (s) *s = d;
   return off;
 }
@@ -396,11 +394,11 @@ int sgr_dspo_ba(const SgrDspoProblem* pr, void* scratch, size_t scratch_bytes, v
   carve(nv, E, M, P, (char*)scratch, &s);
   hipStream_t st = (hipStream_t)stream;
   const float sqrt_alpha = (float)std::sqrt((double)pr->alpha);
-  const int nb = blocks(P);
+  const int nb = blocks_for(P);
 
-  hipLaunchKernelGGL(mark_kernel, dim3(blocks(nv)), dim3(kThreads), 0, st, nv, E, pr->ii, pr->jj, pr->edge_keep, s.flag, s.cnt);
+  hipLaunchKernelGGL(mark_kernel, dim3(blocks_for(nv)), dim3(kThreads), 0, st, nv, E, pr->ii, pr->jj, pr->edge_keep, s.flag, s.cnt);
   hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, st, nv, M, s.flag, s.rank, s.kx, s.cnt, s.ptr, s.status);
-  hipLaunchKernelGGL(fill_kernel, dim3(blocks(E)), dim3(kThreads), 0, st, nv, E, pr->ii, pr->jj, pr->edge_keep, pr->poses, s.ptr,
+  hipLaunchKernelGGL(fill_kernel, dim3(blocks_for(E)), dim3(kThreads), 0, st, nv, E, pr->ii, pr->jj, pr->edge_keep, pr->poses, s.ptr,
                      s.edges);
   for (int it = 0; it < pr->iterations; ++it) {
     hipLaunchKernelGGL(system_kernel, dim3(nb, M), dim3(kThreads), 0, st, P, wd, nb, (const float2*)pr->targets,

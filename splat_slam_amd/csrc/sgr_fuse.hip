@@ -25,7 +25,6 @@ using dba::frame_ok;
 constexpr int kMaxNum = SGR_FUSE_MAX_FRAMES;       // frames per call (a grid dimension)
 constexpr long long kMaxPixels = 1LL << 28;
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
@@ -364,7 +363,7 @@ size_t carve(int num, long long P, bool prepare, char* base, FuseScratch* s) {
   size_t off = 0;
   auto take = [&](size_t bytes) {
     char* p = base ? base + off : nullptr;
-    off += align256(bytes);
+    off += align_up(bytes);
     return p;
   };
   FuseScratch d = {};

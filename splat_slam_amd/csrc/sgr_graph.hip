@@ -25,8 +25,6 @@ constexpr float kMinDepth = 0.2f;           // MIN_DEPTH of projective_ops.py; t
 constexpr float kMotionClamp = 64.f;
 constexpr int kMaxEdges = SGR_GRAPH_MAX_EDGES;      // a grid dimension
 
-inline int blocks(long long n, int per = kThreads) { return (int)((n + per - 1) / per); }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ================================================================================================================================
 // reprojection.  One thread per pixel, blockIdx.y is the edge.  Thread 0 does the pose algebra of the edge once and leaves
@@ -314,7 +312,7 @@ size_t carve_select(int n, char* base, SelArgs* a) {
   size_t off = 0;
   auto take = [&](size_t bytes) {
     char* p = base ? base + off : nullptr;
-    off += align256(bytes);
+    off += align_up(bytes);
     return p;
   };
   float* w = (float*)take((size_t)n * sizeof(float));
@@ -383,7 +381,7 @@ int sgr_graph_reproject(const float* poses, int32_t num_poses, const float* disp
   if (num_edges > kMaxEdges) return set_error(SGR_ERR_CAPACITY, "graph_reproject: %d edges exceed the supported %d", num_edges, kMaxEdges);
   if (num_edges == 0) return SGR_OK;
   const int P = ht * wd, nv = num_poses < num_frames ? num_poses : num_frames;
-  const dim3 grid(blocks(P), num_edges);
+  const dim3 grid(blocks_for(P), num_edges);
   if (motn)
     hipLaunchKernelGGL(reproject_kernel<true>, grid, dim3(kThreads), 0, (hipStream_t)stream, nv, P, wd, poses, disps, intrinsics, ii, jj,
                        target, coords, valid, motn);

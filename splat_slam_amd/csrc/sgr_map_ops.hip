@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "sgr_common.h"
+#include "sgr_scan.h"
 
 namespace sgr {
 int set_error(int code, const char* fmt, ...);
@@ -82,33 +83,13 @@ struct RowTab {
   int32_t count;
 };
 
-// keep mask -> ascending list of kept row indices (deterministic: block scans + an ordered second pass)
+// keep mask -> ascending list of kept row indices (deterministic: block scans, the scan of their totals, an ordered second pass)
 __global__ void __launch_bounds__(256) keep_count_kernel(int64_t n, const uint8_t* __restrict__ keep, uint32_t* __restrict__ block_tot) {
   __shared__ uint32_t red[4];
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   uint32_t tot;
   (void)block256_exclusive_scan((i < n && keep[i]) ? 1u : 0u, red, tot);
   if (threadIdx.x == 0) block_tot[blockIdx.x] = tot;
-}
-__global__ void __launch_bounds__(1024) keep_scan_kernel(int nblocks, uint32_t* __restrict__ block_tot, int64_t* __restrict__ total) {
-  __shared__ uint32_t part[1024];
-  // single block, sequential chunks: nblocks <= a few thousand
-  uint32_t carry = 0;
-  for (int base = 0; base < nblocks; base += 1024) {
-    const int b = base + threadIdx.x;
-    const uint32_t v = b < nblocks ? block_tot[b] : 0u;
-    part[threadIdx.x] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t run = carry;
-      for (int k = 0; k < 1024; ++k) { uint32_t t = part[k]; part[k] = run; run += t; }
-      carry = run;
-    }
-    __syncthreads();
-    if (b < nblocks) block_tot[b] = part[threadIdx.x];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = (int64_t)carry;
 }
 __global__ void __launch_bounds__(256) keep_list_kernel(int64_t n, const uint8_t* __restrict__ keep, const uint32_t* __restrict__ block_base,
                                                         int32_t* __restrict__ src) {
@@ -165,7 +146,7 @@ int sgr_keep_list(int64_t n, const uint8_t* keep, int32_t* src_rows, int64_t* co
   const int nb = (int)((n + 255) / 256);
   uint32_t* bt = (uint32_t*)scratch;
   if (nb > 0) hipLaunchKernelGGL(keep_count_kernel, dim3(nb), dim3(256), 0, st, n, keep, bt);
-  hipLaunchKernelGGL(keep_scan_kernel, dim3(1), dim3(1024), 0, st, nb, bt, count_device);
+  launch_chunked_scan(bt, nb, nullptr, bt, nullptr, nullptr, count_device, st);      // block totals -> block bases, the count
   if (nb > 0) hipLaunchKernelGGL(keep_list_kernel, dim3(nb), dim3(256), 0, st, n, keep, bt, src_rows);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "keep_list launch failed");
 }

@@ -4,14 +4,17 @@
 //                                              each touched unit with one workgroup per unit, frames in order (no float atomics)
 //   sgr_tsdf_extract_count / sgr_tsdf_extract  marching cubes: units sorted by key, count pass, scan, emit pass
 //   sgr_mesh_components / sgr_mesh_compact     union-find labels (minimum vertex id), component sizes, stable compaction
+// (the scans and the compaction kernels: sgr_scan.h)
 // Every assumption about Open3D's semantics is one named constant below (DESIGN.md section 3 lists them): none has been checked
 // against Open3D itself.
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
 
 #include "sgr_common.h"
 #include "sgr_mc_table.h"
+#include "sgr_scan.h"
 
 namespace sgr {
 int set_error(int code, const char* fmt, ...);
@@ -32,7 +35,6 @@ constexpr float kColorScale = 255.f;            // (3) colour (image * 255) trun
 constexpr int kThreads = 256;
 constexpr uint64_t kEmpty = ~0ull;              // bit 63 is never set in a key
 constexpr int kKeyBits = 21, kKeyBias = 1 << (kKeyBits - 1);
-constexpr int kScanItems = 16, kScanBlock = kThreads * kScanItems;
 constexpr int kNb = 27;                         // the 3x3x3 units around a unit
 constexpr int kStateCounters = 8;
 
@@ -63,19 +65,18 @@ struct State {            // carved from SgrTsdfVolume::state
   int32_t* list;          // [cap] touched slots of the chunk
   int32_t* counters;      // [kStateCounters]
 };
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline State carve_state(const SgrTsdfVolume* v) {
   const size_t cap = (size_t)v->hash_capacity;
   char* p = (char*)v->state;
   State s;
   s.keys = (uint64_t*)p;
-  p += align256(cap * 8);
+  p += align_up(cap * 8);
   s.slot_unit = (int32_t*)p;
-  p += align256(cap * 4);
+  p += align_up(cap * 4);
   s.marks = (uint32_t*)p;
-  p += align256(cap * 4);
+  p += align_up(cap * 4);
   s.list = (int32_t*)p;
-  p += align256(cap * 4);
+  p += align_up(cap * 4);
   s.counters = (int32_t*)p;
   return s;
 }
@@ -239,67 +240,6 @@ __global__ void __launch_bounds__(kThreads) tsdf_integrate_kernel(FrameTab tab, 
   }
 }
 
-// ---- scans: exclusive, in place over data[0..n), total to data[n]; blocks of 4096, block sums scanned by one workgroup
-__device__ inline int block_exclusive_scan(int v, int* lds, int& total) {
-  lds[threadIdx.x] = v;
-  __syncthreads();
-  for (int off = 1; off < kThreads; off <<= 1) {
-    const int t = threadIdx.x >= off ? lds[threadIdx.x - off] : 0;
-    __syncthreads();
-    lds[threadIdx.x] += t;
-    __syncthreads();
-  }
-  total = lds[kThreads - 1];
-  const int incl = lds[threadIdx.x];
-  __syncthreads();
-  return incl - v;
-}
-
-__global__ void __launch_bounds__(kThreads) scan_blocks_kernel(int32_t* data, int n, int32_t* sums) {
-  __shared__ int lds[kThreads];
-  const int base = blockIdx.x * kScanBlock + threadIdx.x * kScanItems;
-  int s = 0;
-  for (int i = 0; i < kScanItems; ++i) s += base + i < n ? data[base + i] : 0;
-  int total;
-  int run = block_exclusive_scan(s, lds, total);
-  for (int i = 0; i < kScanItems; ++i)
-    if (base + i < n) {
-      const int v = data[base + i];
-      data[base + i] = run;
-      run += v;
-    }
-  if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-__global__ void __launch_bounds__(kThreads) scan_sums_kernel(int32_t* sums, int nb, int32_t* total_out) {
-  __shared__ int lds[kThreads];
-  int carry = 0;
-  for (int c0 = 0; c0 < nb; c0 += kThreads) {
-    const int i = c0 + threadIdx.x;
-    const int v = i < nb ? sums[i] : 0;
-    int total;
-    const int ex = block_exclusive_scan(v, lds, total);
-    if (i < nb) sums[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) *total_out = carry;
-}
-
-__global__ void __launch_bounds__(kThreads) scan_add_kernel(int32_t* data, int n, const int32_t* sums) {
-  const int add = sums[blockIdx.x];
-  const int base = blockIdx.x * kScanBlock;
-  for (int i = threadIdx.x; i < kScanBlock; i += kThreads)
-    if (base + i < n) data[base + i] += add;
-}
-
-inline int scan_blocks(int n) { return (n + kScanBlock - 1) / kScanBlock; }
-void scan_exclusive(int32_t* data, int n, int32_t* sums, hipStream_t st) {
-  const int nb = scan_blocks(n) > 0 ? scan_blocks(n) : 1;
-  hipLaunchKernelGGL(scan_blocks_kernel, dim3(nb), dim3(kThreads), 0, st, data, n, sums);
-  hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kThreads), 0, st, sums, nb, data + n);
-  hipLaunchKernelGGL(scan_add_kernel, dim3(nb), dim3(kThreads), 0, st, data, n, (const int32_t*)sums);
-}
-
 // ---- extraction
 __global__ void __launch_bounds__(kThreads) gather_units_kernel(const uint64_t* keys, const int32_t* slot_unit, int cap,
                                                                 uint64_t* skeys, int32_t* sunit, int32_t* cursor) {
@@ -343,20 +283,20 @@ inline Extract carve_extract(void* scratch, int cap, int pool_capacity) {
   char* p = (char*)scratch;
   Extract e;
   const size_t sn = (size_t)sort_len(cap);
-  e.skeys = (uint64_t*)p; p += align256(sn * 8);
-  e.sunit = (int32_t*)p; p += align256(sn * 4);
-  e.rank = (int32_t*)p; p += align256((size_t)pool_capacity * 4);
-  e.nb = (int32_t*)p; p += align256((size_t)cap * kNb * 4);
-  e.cnt_v = (int32_t*)p; p += align256(((size_t)cap + 1) * 4);
-  e.cnt_t = (int32_t*)p; p += align256(((size_t)cap + 1) * 4);
-  e.sums = (int32_t*)p; p += align256(((size_t)scan_blocks(cap) + 1) * 4);
+  e.skeys = (uint64_t*)p; p += align_up(sn * 8);
+  e.sunit = (int32_t*)p; p += align_up(sn * 4);
+  e.rank = (int32_t*)p; p += align_up((size_t)pool_capacity * 4);
+  e.nb = (int32_t*)p; p += align_up((size_t)cap * kNb * 4);
+  e.cnt_v = (int32_t*)p; p += align_up(((size_t)cap + 1) * 4);
+  e.cnt_t = (int32_t*)p; p += align_up(((size_t)cap + 1) * 4);
+  e.sums = (int32_t*)p; p += align_up(((size_t)scan_blocks(cap) + 1) * 4);
   e.cursor = (int32_t*)p; p += 256;
-  e.vinfo = (uint32_t*)p; p += align256((size_t)pool_capacity * kUnitVox * 4);
+  e.vinfo = (uint32_t*)p; p += align_up((size_t)pool_capacity * kUnitVox * 4);
   return e;
 }
 inline size_t extract_bytes(int cap, int pool_capacity) {
   Extract e = carve_extract(nullptr, cap, pool_capacity);
-  return (size_t)((char*)e.vinfo - (char*)nullptr) + align256((size_t)pool_capacity * kUnitVox * 4);
+  return (size_t)((char*)e.vinfo - (char*)nullptr) + align_up((size_t)pool_capacity * kUnitVox * 4);
 }
 
 // voxel (x, y, z) in [-1, 17) of the unit whose neighbours are nb: pool unit (-1: none) and voxel index
@@ -426,7 +366,7 @@ __device__ inline void load_neighbours(const uint64_t* keys, const int32_t* slot
 __global__ void __launch_bounds__(kThreads) mc_count_kernel(const uint64_t* keys, const int32_t* slot_unit, uint32_t mask,
                                                             const float* pool, Extract e) {
   __shared__ int nb[kNb];
-  __shared__ int lds[kThreads];
+  __shared__ uint32_t red[kThreads / 64];
   const int i = blockIdx.x;
   load_neighbours(keys, slot_unit, mask, e.skeys[i], nb);
   __syncthreads();
@@ -441,17 +381,17 @@ __global__ void __launch_bounds__(kThreads) mc_count_kernel(const uint64_t* keys
     const int ci = cube_case(pool, nb, x, y, z);
     nt += ci < 0 ? 0 : mc::kNumTris[ci];
   }
-  int tv, tt;
-  int off = block_exclusive_scan(nv, lds, tv);
-  block_exclusive_scan(nt, lds, tt);
+  uint32_t tv, tt;
+  int off = (int)block_exclusive_scan<kThreads / 64>((uint32_t)nv, red, tv);
+  block_exclusive_scan<kThreads / 64>((uint32_t)nt, red, tt);
   uint32_t* vinfo = e.vinfo + (size_t)nb[13] * kUnitVox + kUnitRes * threadIdx.x;
   for (int x = 0; x < kUnitRes; ++x) {
     vinfo[x] = ((uint32_t)off << 3) | (uint32_t)masks[x];
     off += __popc(masks[x]);
   }
   if (threadIdx.x == 0) {
-    e.cnt_v[i] = tv;
-    e.cnt_t[i] = tt;
+    e.cnt_v[i] = (int32_t)tv;
+    e.cnt_t[i] = (int32_t)tt;
   }
 }
 
@@ -459,7 +399,7 @@ __global__ void __launch_bounds__(kThreads) mc_count_kernel(const uint64_t* keys
 __global__ void __launch_bounds__(kThreads) mc_emit_kernel(const float* pool, float voxel_len, Extract e, float* __restrict__ verts,
                                                            float* __restrict__ colors, int32_t* __restrict__ tris) {
   __shared__ int nb[kNb];
-  __shared__ int lds[kThreads];
+  __shared__ uint32_t red[kThreads / 64];
   const int i = blockIdx.x;
   if (threadIdx.x < kNb) nb[threadIdx.x] = e.nb[(size_t)i * kNb + threadIdx.x];
   __syncthreads();
@@ -502,8 +442,8 @@ __global__ void __launch_bounds__(kThreads) mc_emit_kernel(const float* pool, fl
     cases[x] = cube_case(pool, nb, x, y, z);
     nt += cases[x] < 0 ? 0 : mc::kNumTris[cases[x]];
   }
-  int tt;
-  int tid = e.cnt_t[i] + block_exclusive_scan(nt, lds, tt);
+  uint32_t tt;
+  int tid = e.cnt_t[i] + (int)block_exclusive_scan<kThreads / 64>((uint32_t)nt, red, tt);
   for (int x = 0; x < kUnitRes; ++x) {
     const int ci = cases[x];
     if (ci < 0) continue;
@@ -536,19 +476,19 @@ struct Clean {            // carved from the cleaning scratch
 inline Clean carve_clean(void* scratch, int V, int F) {
   char* p = (char*)scratch;
   Clean c;
-  c.label = (int32_t*)p; p += align256((size_t)V * 4);
-  c.csize = (int32_t*)p; p += align256((size_t)V * 4);
-  c.vnew = (int32_t*)p; p += align256(((size_t)V + 1) * 4);
-  c.tnew = (int32_t*)p; p += align256(((size_t)F + 1) * 4);
-  c.bcount = (int32_t*)p; p += align256(((size_t)V + 1) * 4);
-  c.bfill = (int32_t*)p; p += align256((size_t)V * 4);
-  c.bucket = (int32_t*)p; p += align256((size_t)F * 4);
+  c.label = (int32_t*)p; p += align_up((size_t)V * 4);
+  c.csize = (int32_t*)p; p += align_up((size_t)V * 4);
+  c.vnew = (int32_t*)p; p += align_up(((size_t)V + 1) * 4);
+  c.tnew = (int32_t*)p; p += align_up(((size_t)F + 1) * 4);
+  c.bcount = (int32_t*)p; p += align_up(((size_t)V + 1) * 4);
+  c.bfill = (int32_t*)p; p += align_up((size_t)V * 4);
+  c.bucket = (int32_t*)p; p += align_up((size_t)F * 4);
   c.sums = (int32_t*)p;
   return c;
 }
 inline size_t clean_bytes(int V, int F) {
   Clean c = carve_clean(nullptr, V, F);
-  return (size_t)((char*)c.sums - (char*)nullptr) + align256(((size_t)scan_blocks(V > F ? V : F) + 1) * 4);
+  return (size_t)((char*)c.sums - (char*)nullptr) + align_up(((size_t)scan_blocks(V > F ? V : F) + 1) * 4);
 }
 
 __device__ inline int find_root(int32_t* label, int x) {
@@ -659,30 +599,6 @@ __global__ void __launch_bounds__(kThreads) tri_dedup_kernel(int F, const int32_
   }
 }
 
-__global__ void __launch_bounds__(kThreads) compact_vertices_kernel(int V, const float* verts, const float* colors, Clean c,
-                                                                    float* out_v, float* out_c, int32_t* vmap) {
-  const int v = blockIdx.x * kThreads + threadIdx.x;
-  if (v >= V) return;
-  const int n = c.vnew[v];
-  const bool keep = c.vnew[v + 1] != n;
-  if (vmap) vmap[v] = keep ? n : -1;
-  if (!keep) return;
-  for (int k = 0; k < 3; ++k) {
-    out_v[(size_t)n * 3 + k] = verts[(size_t)v * 3 + k];
-    out_c[(size_t)n * 3 + k] = colors[(size_t)v * 3 + k];
-  }
-}
-
-__global__ void __launch_bounds__(kThreads) compact_triangles_kernel(int F, const int32_t* tris, Clean c, int32_t* out_t) {
-  const int t = blockIdx.x * kThreads + threadIdx.x;
-  if (t >= F) return;
-  const int n = c.tnew[t];
-  if (c.tnew[t + 1] == n) return;
-  for (int k = 0; k < 3; ++k) out_t[(size_t)n * 3 + k] = c.vnew[tris[(size_t)t * 3 + k]];
-}
-
-inline int blocks(long long n) { return (int)((n + kThreads - 1) / kThreads) > 0 ? (int)((n + kThreads - 1) / kThreads) : 1; }
-
 bool volume_ok(const SgrTsdfVolume* v) {
   return v && v->state && v->pool && v->hash_capacity >= 64 && (v->hash_capacity & (v->hash_capacity - 1)) == 0 &&
          v->pool_capacity > 0 && v->voxel_length > 0.f && v->sdf_trunc > 0.f && v->depth_trunc > 0.f;
@@ -738,7 +654,7 @@ extern "C" {
 size_t sgr_tsdf_bytes(int32_t hash_capacity) {
   if (hash_capacity <= 0) return 0;
   const size_t cap = (size_t)hash_capacity;
-  return align256(cap * 8) + 3 * align256(cap * 4) + align256(kStateCounters * 4);
+  return align_up(cap * 8) + 3 * align_up(cap * 4) + align_up(kStateCounters * 4);
 }
 
 int sgr_tsdf_reset(const SgrTsdfVolume* vol, void* stream) {
@@ -761,7 +677,7 @@ int sgr_tsdf_rehash(const SgrTsdfVolume* src, const SgrTsdfVolume* dst, void* st
   State a = carve_state(src), b = carve_state(dst);
   if (hipMemcpyAsync(b.counters, a.counters, sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess)
     return set_error(SGR_ERR_HIP, "tsdf_rehash: copy failed");
-  hipLaunchKernelGGL(tsdf_rehash_kernel, dim3(blocks(src->hash_capacity)), dim3(kThreads), 0, st, (const uint64_t*)a.keys,
+  hipLaunchKernelGGL(tsdf_rehash_kernel, dim3(blocks_for(src->hash_capacity)), dim3(kThreads), 0, st, (const uint64_t*)a.keys,
                      (const int32_t*)a.slot_unit, src->hash_capacity, b.keys, b.slot_unit, b.counters,
                      (uint32_t)dst->hash_capacity - 1u);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "tsdf_rehash launch failed");
@@ -776,9 +692,9 @@ int sgr_tsdf_touch(const SgrTsdfVolume* vol, int32_t n, const SgrTsdfFrame* fram
   State s = carve_state(vol);
   if (hipMemsetAsync(s.counters + 2, 0, sizeof(int32_t), st) != hipSuccess) return set_error(SGR_ERR_HIP, "tsdf_touch: memset");
   const long long pts = (long long)((W + kTouchStride - 1) / kTouchStride) * ((H + kTouchStride - 1) / kTouchStride);
-  hipLaunchKernelGGL(tsdf_touch_kernel, dim3(blocks(pts), n), dim3(kThreads), 0, st, tab, H, W, vol->voxel_length * kUnitRes,
+  hipLaunchKernelGGL(tsdf_touch_kernel, dim3(blocks_for(pts), n), dim3(kThreads), 0, st, tab, H, W, vol->voxel_length * kUnitRes,
                      vol->sdf_trunc, vol->depth_trunc, s.keys, s.slot_unit, s.marks, s.counters, (uint32_t)vol->hash_capacity - 1u);
-  hipLaunchKernelGGL(tsdf_list_kernel, dim3(blocks(vol->hash_capacity)), dim3(kThreads), 0, st, (const uint32_t*)s.marks,
+  hipLaunchKernelGGL(tsdf_list_kernel, dim3(blocks_for(vol->hash_capacity)), dim3(kThreads), 0, st, (const uint32_t*)s.marks,
                      vol->hash_capacity, s.list, s.counters);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "tsdf_touch launch failed");
 }
@@ -817,11 +733,11 @@ int sgr_tsdf_extract_count(const SgrTsdfVolume* vol, int32_t n_units, void* scra
   const int sn = sort_len(n_units < 2 ? 2 : n_units);
   if (hipMemsetAsync(e.skeys, 0xff, (size_t)sn * 8, st) != hipSuccess || hipMemsetAsync(e.cursor, 0, 4, st) != hipSuccess)
     return set_error(SGR_ERR_HIP, "tsdf_extract_count: memset");
-  hipLaunchKernelGGL(gather_units_kernel, dim3(blocks(vol->hash_capacity)), dim3(kThreads), 0, st, (const uint64_t*)s.keys,
+  hipLaunchKernelGGL(gather_units_kernel, dim3(blocks_for(vol->hash_capacity)), dim3(kThreads), 0, st, (const uint64_t*)s.keys,
                      (const int32_t*)s.slot_unit, vol->hash_capacity, e.skeys, e.sunit, e.cursor);
   for (int k = 2; k <= sn; k <<= 1)
     for (int j = k >> 1; j > 0; j >>= 1)
-      hipLaunchKernelGGL(bitonic_step_kernel, dim3(blocks(sn)), dim3(kThreads), 0, st, e.skeys, e.sunit, sn, k, j);
+      hipLaunchKernelGGL(bitonic_step_kernel, dim3(blocks_for(sn)), dim3(kThreads), 0, st, e.skeys, e.sunit, sn, k, j);
   hipLaunchKernelGGL(mc_count_kernel, dim3(n_units), dim3(kThreads), 0, st, (const uint64_t*)s.keys, (const int32_t*)s.slot_unit,
                      (uint32_t)vol->hash_capacity - 1u, (const float*)vol->pool, e);
   scan_exclusive(e.cnt_v, n_units, e.sums, st);
@@ -858,16 +774,17 @@ int sgr_mesh_components(int32_t V, int32_t F, const float* vertices, const int32
   if (!scratch || scratch_bytes < clean_bytes(V, F)) return set_error(SGR_ERR_WORKSPACE, "mesh_components: scratch too small");
   hipStream_t st = (hipStream_t)stream;
   Clean c = carve_clean(scratch, V, F);
-  hipLaunchKernelGGL(cc_init_kernel, dim3(blocks(V)), dim3(kThreads), 0, st, V, c);
-  if (F > 0) hipLaunchKernelGGL(cc_union_kernel, dim3(blocks(F)), dim3(kThreads), 0, st, F, triangles, c);
-  hipLaunchKernelGGL(cc_flatten_kernel, dim3(blocks(V)), dim3(kThreads), 0, st, V, c);
-  hipLaunchKernelGGL(cc_keep_vertices_kernel, dim3(blocks(V)), dim3(kThreads), 0, st, V, min_len, c);
+  const int vb = std::max(1, blocks_for(V));      // V == 0: one idle workgroup, not an empty grid
+  hipLaunchKernelGGL(cc_init_kernel, dim3(vb), dim3(kThreads), 0, st, V, c);
+  if (F > 0) hipLaunchKernelGGL(cc_union_kernel, dim3(blocks_for(F)), dim3(kThreads), 0, st, F, triangles, c);
+  hipLaunchKernelGGL(cc_flatten_kernel, dim3(vb), dim3(kThreads), 0, st, V, c);
+  hipLaunchKernelGGL(cc_keep_vertices_kernel, dim3(vb), dim3(kThreads), 0, st, V, min_len, c);
   scan_exclusive(c.vnew, V, c.sums, st);
   if (F > 0) {
-    hipLaunchKernelGGL(tri_keep_kernel, dim3(blocks(F)), dim3(kThreads), 0, st, F, triangles, vertices, min_len, c);
+    hipLaunchKernelGGL(tri_keep_kernel, dim3(blocks_for(F)), dim3(kThreads), 0, st, F, triangles, vertices, min_len, c);
     scan_exclusive(c.bcount, V, c.sums, st);
-    hipLaunchKernelGGL(tri_bucket_kernel, dim3(blocks(F)), dim3(kThreads), 0, st, F, triangles, c);
-    hipLaunchKernelGGL(tri_dedup_kernel, dim3(blocks(F)), dim3(kThreads), 0, st, F, triangles, c);
+    hipLaunchKernelGGL(tri_bucket_kernel, dim3(blocks_for(F)), dim3(kThreads), 0, st, F, triangles, c);
+    hipLaunchKernelGGL(tri_dedup_kernel, dim3(blocks_for(F)), dim3(kThreads), 0, st, F, triangles, c);
   }
   scan_exclusive(c.tnew, F, c.sums, st);
   if (hipMemcpyAsync(totals, c.vnew + V, 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
@@ -882,12 +799,8 @@ int sgr_mesh_compact(int32_t V, int32_t F, const float* vertices, const float* c
   if (V < 0 || F < 0 || (V > 0 && (!vertices || !colors)) || (F > 0 && !triangles))
     return set_error(SGR_ERR_INVALID, "mesh_compact: bad arguments");
   if (!scratch || scratch_bytes < clean_bytes(V, F)) return set_error(SGR_ERR_WORKSPACE, "mesh_compact: scratch too small");
-  hipStream_t st = (hipStream_t)stream;
-  Clean c = carve_clean(scratch, V, F);
-  if (V > 0)
-    hipLaunchKernelGGL(compact_vertices_kernel, dim3(blocks(V)), dim3(kThreads), 0, st, V, vertices, colors, c, out_vertices,
-                       out_colors, vertex_map);
-  if (F > 0) hipLaunchKernelGGL(compact_triangles_kernel, dim3(blocks(F)), dim3(kThreads), 0, st, F, triangles, c, out_triangles);
+  const Clean c = carve_clean(scratch, V, F);
+  launch_mesh_compact(V, F, vertices, colors, triangles, c.vnew, c.tnew, out_vertices, out_colors, out_triangles, vertex_map, (hipStream_t)stream);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "mesh_compact launch failed");
 }
 

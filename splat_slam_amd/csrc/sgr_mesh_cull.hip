@@ -5,7 +5,7 @@
 //                         perspective-correct fp32 depth, integer atomicMin on the bit pattern of the (positive) depth
 //   sgr_cull_visibility   one thread per vertex: the number of frames that see it (frustum, far, depth map within eps)
 //   sgr_cull_select       faces whose vertices were seen often enough, vertices they still reference: two exclusive scans
-//   sgr_cull_compact      vertices, colours and faces in their original order, reindexed
+//   sgr_cull_compact      vertices, colours and faces in their original order, reindexed (scans and compaction: sgr_scan.h)
 // Everything after the projection is integer or single-operation fp32 arithmetic: tests/mesh_cull_ref.py restates it bit for bit.
 // No float atomics: the z-buffer does not depend on the order of the triangles.
 #include <algorithm>
@@ -13,6 +13,7 @@
 #include <cstdint>
 
 #include "sgr_common.h"
+#include "sgr_scan.h"
 
 namespace sgr {
 int set_error(int code, const char* fmt, ...);
@@ -20,14 +21,11 @@ int set_error(int code, const char* fmt, ...);
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kScanItems = 16, kScanBlock = kThreads * kScanItems;
 constexpr int kSub = 1 << SGR_CULL_SUBPIXEL_BITS;                   // snapped units per pixel
 constexpr int kGuardSub = SGR_CULL_GUARD_PIXELS * kSub;             // |snapped coordinate| of a valid vertex is at most this
 constexpr int kSmallBox = 8;                                        // a bounding box of at most 8 x 8 pixels is its thread's own loop
 constexpr int kLargeBlocks = 1024;                                  // grid of the wave-per-triangle pass (strides over the list)
 constexpr uint32_t kInfBits = 0x7f800000u;
-
-inline int blocks(long long n) { const long long b = (n + kThreads - 1) / kThreads; return b > 0 ? (int)b : 1; }
 
 struct FrameTab { SgrCullFrame f[SGR_CULL_MAX_FRAMES]; };
 
@@ -193,7 +191,6 @@ __global__ void __launch_bounds__(kThreads) cull_visibility_kernel(int V, int n,
 
 // ---- selection
 struct Select { int32_t *vnew, *tnew, *sums; };      // vnew [V + 1], tnew [F + 1]: flags, then exclusive prefixes with the total last
-inline int scan_blocks(int n) { const int b = (n + kScanBlock - 1) / kScanBlock; return b > 0 ? b : 1; }
 inline size_t select_bytes(int V, int F) {
   return align_up(((size_t)V + 1) * 4) + align_up(((size_t)F + 1) * 4) + align_up(((size_t)scan_blocks(V > F ? V : F) + 1) * 4);
 }
@@ -220,71 +217,6 @@ __global__ void __launch_bounds__(kThreads) cull_face_keep_kernel(int V, int F, 
   if (keep) { s.vnew[a] = 1; s.vnew[b] = 1; s.vnew[c] = 1; }      // (vnew was zeroed; every writer writes 1)
 }
 
-// exclusive scan of data[0..n) in place, the total into data[n]: per workgroup, then the workgroup totals, then the add
-__global__ void __launch_bounds__(kThreads) cull_scan_local_kernel(int32_t* __restrict__ data, int n, int32_t* __restrict__ sums) {
-  __shared__ uint32_t red[4];
-  const int base = blockIdx.x * kScanBlock + threadIdx.x * kScanItems;
-  uint32_t s = 0;
-  for (int k = 0; k < kScanItems; ++k) s += base + k < n ? (uint32_t)data[base + k] : 0u;
-  uint32_t total;
-  uint32_t run = block256_exclusive_scan(s, red, total);
-  for (int k = 0; k < kScanItems; ++k)
-    if (base + k < n) {
-      const uint32_t v = (uint32_t)data[base + k];
-      data[base + k] = (int32_t)run;
-      run += v;
-    }
-  if (threadIdx.x == 0) sums[blockIdx.x] = (int32_t)total;
-}
-
-__global__ void __launch_bounds__(kThreads) cull_scan_sums_kernel(int32_t* __restrict__ sums, int nb, int32_t* __restrict__ total_out) {
-  __shared__ uint32_t red[4];
-  uint32_t carry = 0;
-  for (int c0 = 0; c0 < nb; c0 += kThreads) {
-    const int i = c0 + threadIdx.x;
-    const uint32_t v = i < nb ? (uint32_t)sums[i] : 0u;
-    uint32_t total;
-    const uint32_t ex = block256_exclusive_scan(v, red, total);
-    if (i < nb) sums[i] = (int32_t)(carry + ex);
-    carry += total;
-  }
-  if (threadIdx.x == 0) *total_out = (int32_t)carry;
-}
-
-__global__ void __launch_bounds__(kThreads) cull_scan_add_kernel(int32_t* __restrict__ data, int n, const int32_t* __restrict__ sums) {
-  const int i = blockIdx.x * kThreads + threadIdx.x;
-  if (i < n) data[i] += sums[i / kScanBlock];
-}
-
-void scan_exclusive(int32_t* data, int n, int32_t* sums, hipStream_t st) {
-  const int nb = scan_blocks(n);
-  hipLaunchKernelGGL(cull_scan_local_kernel, dim3(nb), dim3(kThreads), 0, st, data, n, sums);
-  hipLaunchKernelGGL(cull_scan_sums_kernel, dim3(1), dim3(kThreads), 0, st, sums, nb, data + n);
-  if (n > 0) hipLaunchKernelGGL(cull_scan_add_kernel, dim3(blocks(n)), dim3(kThreads), 0, st, data, n, (const int32_t*)sums);
-}
-
-__global__ void __launch_bounds__(kThreads) cull_compact_vertices_kernel(int V, const float* __restrict__ verts, const float* __restrict__ colors,
-                                                                         Select s, float* __restrict__ out_v, float* __restrict__ out_c,
-                                                                         int32_t* __restrict__ vmap) {
-  const int v = blockIdx.x * kThreads + threadIdx.x;
-  if (v >= V) return;
-  const int n = s.vnew[v];
-  const bool keep = s.vnew[v + 1] != n;
-  if (vmap) vmap[v] = keep ? n : -1;
-  if (!keep) return;
-  st3(out_v + 3 * (size_t)n, ld3(verts + 3 * (size_t)v));
-  st3(out_c + 3 * (size_t)n, ld3(colors + 3 * (size_t)v));
-}
-
-__global__ void __launch_bounds__(kThreads) cull_compact_triangles_kernel(int F, const int32_t* __restrict__ tris, Select s,
-                                                                          int32_t* __restrict__ out_t) {
-  const int t = blockIdx.x * kThreads + threadIdx.x;
-  if (t >= F) return;
-  const int n = s.tnew[t];
-  if (s.tnew[t + 1] == n) return;
-  for (int k = 0; k < 3; ++k) out_t[3 * (size_t)n + k] = s.vnew[tris[3 * (size_t)t + k]];
-}
-
 inline size_t raster_bytes(int F, int n) { return 256 + align_up((size_t)F * (size_t)n * 8); }
 
 }  // namespace
@@ -300,7 +232,7 @@ int sgr_cull_project(int32_t V, const float* vertices, int32_t n, const SgrCullF
     return set_error(SGR_ERR_INVALID, "cull_project: bad arguments (V=%d n=%d near=%g)", V, n, near);
   FrameTab tab{};
   for (int f = 0; f < n; ++f) tab.f[f] = frames[f];
-  hipLaunchKernelGGL(cull_project_kernel, dim3(blocks(V), n), dim3(kThreads), 0, (hipStream_t)stream, V, vertices, tab, near, xy, z);
+  hipLaunchKernelGGL(cull_project_kernel, dim3(blocks_for(V), n), dim3(kThreads), 0, (hipStream_t)stream, V, vertices, tab, near, xy, z);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "cull_project launch failed");
 }
 
@@ -322,7 +254,7 @@ int sgr_cull_raster(int32_t V, int32_t F, const int32_t* triangles, int32_t n, c
       hipMemsetAsync(count, 0, 256, st) != hipSuccess || (skipped && hipMemsetAsync(skipped, 0, (size_t)n * 4, st) != hipSuccess))
     return set_error(SGR_ERR_HIP, "cull_raster: memset");
   if (F > 0) {
-    hipLaunchKernelGGL(cull_raster_small_kernel, dim3(blocks(F), n), dim3(kThreads), 0, st, V, F, triangles, xy, z, H, W, (uint32_t*)depth,
+    hipLaunchKernelGGL(cull_raster_small_kernel, dim3(blocks_for(F), n), dim3(kThreads), 0, st, V, F, triangles, xy, z, H, W, (uint32_t*)depth,
                        skipped, count, large);
     const long long pairs = (long long)F * n;
     const int grid = (int)std::min<long long>(kLargeBlocks, (pairs + kThreads / 64 - 1) / (kThreads / 64));
@@ -336,7 +268,7 @@ int sgr_cull_visibility(int32_t V, int32_t n, const int32_t* xy, const float* z,
                         float far, float eps, int32_t* seen, void* stream) {
   if (V <= 0 || n < 1 || n > SGR_CULL_MAX_FRAMES || H < 1 || W < 1 || edge < 0 || !xy || !z || !seen || !(far > 0.f) || std::isnan(eps))
     return set_error(SGR_ERR_INVALID, "cull_visibility: bad arguments (V=%d n=%d H=%d W=%d edge=%d)", V, n, H, W, edge);
-  hipLaunchKernelGGL(cull_visibility_kernel, dim3(blocks(V)), dim3(kThreads), 0, (hipStream_t)stream, V, n, xy, z, depth, H, W, edge, far,
+  hipLaunchKernelGGL(cull_visibility_kernel, dim3(blocks_for(V)), dim3(kThreads), 0, (hipStream_t)stream, V, n, xy, z, depth, H, W, edge, far,
                      eps, seen);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "cull_visibility launch failed");
 }
@@ -356,7 +288,7 @@ int sgr_cull_select(int32_t V, int32_t F, const int32_t* triangles, const int32_
   Select s = carve_select(scratch, V, F);
   if (hipMemsetAsync(s.vnew, 0, ((size_t)V + 1) * 4, st) != hipSuccess) return set_error(SGR_ERR_HIP, "cull_select: memset");
   if (F > 0 && V > 0)
-    hipLaunchKernelGGL(cull_face_keep_kernel, dim3(blocks(F)), dim3(kThreads), 0, st, V, F, triangles, seen, min_views,
+    hipLaunchKernelGGL(cull_face_keep_kernel, dim3(blocks_for(F)), dim3(kThreads), 0, st, V, F, triangles, seen, min_views,
                        rule == SGR_CULL_RULE_ANY ? 1 : 0, s);
   else if (hipMemsetAsync(s.tnew, 0, ((size_t)F + 1) * 4, st) != hipSuccess)
     return set_error(SGR_ERR_HIP, "cull_select: memset");
@@ -374,12 +306,8 @@ int sgr_cull_compact(int32_t V, int32_t F, const float* vertices, const float* c
   if (V < 0 || F < 0 || (V > 0 && (!vertices || !colors)) || (F > 0 && !triangles))
     return set_error(SGR_ERR_INVALID, "cull_compact: bad arguments (V=%d F=%d)", V, F);
   if (!scratch || scratch_bytes < select_bytes(V, F)) return set_error(SGR_ERR_WORKSPACE, "cull_compact: scratch too small");
-  hipStream_t st = (hipStream_t)stream;
-  Select s = carve_select(scratch, V, F);
-  if (V > 0)
-    hipLaunchKernelGGL(cull_compact_vertices_kernel, dim3(blocks(V)), dim3(kThreads), 0, st, V, vertices, colors, s, out_vertices,
-                       out_colors, vertex_map);
-  if (F > 0) hipLaunchKernelGGL(cull_compact_triangles_kernel, dim3(blocks(F)), dim3(kThreads), 0, st, F, triangles, s, out_triangles);
+  const Select s = carve_select(scratch, V, F);
+  launch_mesh_compact(V, F, vertices, colors, triangles, s.vnew, s.tnew, out_vertices, out_colors, out_triangles, vertex_map, (hipStream_t)stream);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "cull_compact launch failed");
 }
 

@@ -3,16 +3,16 @@
 // conventions are the ones listed in DESIGN.md section 3, "Mesh evaluation":
 //   sgr_surface_sample                       area-weighted surface samples: fp64 areas, fp64 inclusive scan, one thread per sample
 //                                            (counter-based hash -> binary search over the CDF -> sqrt-barycentric point)
-//   sgr_nn_grid_build / sgr_nn_query         exact nearest neighbours through a uniform grid over the target cloud (counting sort
-//                                            into cells); the query walks rings of cells until the best distance is proven
+//   sgr_nn_grid_build / sgr_nn_query         exact nearest neighbours through a uniform grid over the target cloud (sgr_point_grid.h);
+//                                            the query walks rings of cells until the best distance is proven
 //   sgr_icp_accumulate                       fp64 correspondence sums of one point-to-point ICP step (the SVD runs on the host)
 //   sgr_cloud_metrics                        sums and threshold counts of the two distance arrays
 // Reductions are per-workgroup partials followed by one fixed-order pass: no float atomics, bitwise reproducible.
-#include <algorithm>
 #include <cmath>
 #include <cstdint>
 
 #include "sgr_common.h"
+#include "sgr_point_grid.h"
 
 namespace sgr {
 int set_error(int code, const char* fmt, ...);
@@ -23,9 +23,7 @@ constexpr int kThreads = 256;
 constexpr int kScanItems = 16, kScanBlock = kThreads * kScanItems;   // fp64 CDF scan: 4096 faces per workgroup
 constexpr int kRedBlocks = 256;                                      // partial workgroups of every reduction (fixed: fixed order)
 constexpr int kIcpSums = 17;                                         // count, sum d^2, sum p (3), sum q (3), sum p q^T (9)
-constexpr float kCellSlack = 8e-6f;                                  // fp32 rounding of a cell coordinate, relative to |coords|
 
-inline int blocks(long long n) { return (int)((n + kThreads - 1) / kThreads); }
 
 // ---- counter-based uniforms: splitmix64 finaliser over (seed, sample, stream); independent of the launch shape
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {
@@ -142,135 +140,7 @@ __global__ void __launch_bounds__(kThreads) sample_kernel(int n, int V, int F, c
   out_tri[i] = f;
 }
 
-// ---- nearest-neighbour grid (the pattern of sgr_aux.hip's knn grid, extended to outside queries, max_dist and index ties)
-struct NnGrid { float lo[3], hi[3]; float h, inv_h, eps; int g[3]; int gmax; int cells; int n; };
-struct NnXform { float m[12]; int on; };     // rows of [R | t]; on == 0: identity
-
-__device__ __forceinline__ uint32_t ordered(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
-__device__ __forceinline__ float unordered(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
-__device__ __forceinline__ F3 apply(const NnXform& T, F3 p) {
-  if (!T.on) return p;
-  return {T.m[0] * p.x + T.m[1] * p.y + T.m[2] * p.z + T.m[3], T.m[4] * p.x + T.m[5] * p.y + T.m[6] * p.z + T.m[7],
-          T.m[8] * p.x + T.m[9] * p.y + T.m[10] * p.z + T.m[11]};
-}
-__device__ __forceinline__ int cell_coord(float v, float lo, float inv_h, int g) { return min(g - 1, max(0, (int)floorf((v - lo) * inv_h))); }
-inline size_t max_cells(int n) { return (size_t)n / 2 + 1024; }
-
-struct Blob { NnGrid* grid; uint32_t *mm, *count, *start, *cursor, *cell_of, *sidx; float* sxyz; };
-inline Blob carve(void* blob, int n) {
-  char* p = (char*)blob;
-  const size_t mc = max_cells(n);
-  Blob b;
-  b.grid = (NnGrid*)p; p += 256;
-  b.mm = (uint32_t*)p; p += 256;
-  b.count = (uint32_t*)p; p += align_up(mc * 4);
-  b.start = (uint32_t*)p; p += align_up(mc * 4);
-  b.cursor = (uint32_t*)p; p += align_up(mc * 4);
-  b.cell_of = (uint32_t*)p; p += align_up((size_t)n * 4);
-  b.sidx = (uint32_t*)p; p += align_up((size_t)n * 4);
-  b.sxyz = (float*)p;
-  return b;
-}
-inline size_t blob_bytes(int n) { const size_t mc = max_cells(n); return 512 + 3 * align_up(mc * 4) + 2 * align_up((size_t)n * 4) + align_up((size_t)n * 12); }
-
-__global__ void __launch_bounds__(kThreads) nn_bounds_kernel(int n, const float* __restrict__ xyz, NnXform T, uint32_t* __restrict__ mm) {
-  __shared__ float red[4][6];
-  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-  for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) {
-    const F3 p = apply(T, ld3(xyz + 3 * (size_t)i));
-    lo[0] = fminf(lo[0], p.x); hi[0] = fmaxf(hi[0], p.x);
-    lo[1] = fminf(lo[1], p.y); hi[1] = fmaxf(hi[1], p.y);
-    lo[2] = fminf(lo[2], p.z); hi[2] = fmaxf(hi[2], p.z);
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    for (int off = 32; off > 0; off >>= 1) { lo[k] = fminf(lo[k], __shfl_xor(lo[k], off)); hi[k] = fmaxf(hi[k], __shfl_xor(hi[k], off)); }
-    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][k] = lo[k]; red[threadIdx.x >> 6][3 + k] = hi[k]; }
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {            // integer min / max on order-preserving keys
-    const int k = threadIdx.x;
-    if (k < 3) atomicMin(&mm[k], ordered(fminf(fminf(red[0][k], red[1][k]), fminf(red[2][k], red[3][k]))));
-    else atomicMax(&mm[k], ordered(fmaxf(fmaxf(red[0][k], red[1][k]), fmaxf(red[2][k], red[3][k]))));
-  }
-}
-
-__global__ void nn_setup_kernel(int n, int mcells, const uint32_t* __restrict__ mm, NnGrid* __restrict__ out) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  NnGrid G;
-  float ext[3], amax = 0.f;
-  for (int k = 0; k < 3; ++k) {
-    float lo = unordered(mm[k]), hi = unordered(mm[3 + k]);
-    if (!(lo <= hi)) lo = hi = 0.f;          // only non-finite points: one cell at the origin
-    G.lo[k] = lo; G.hi[k] = hi;
-    ext[k] = hi - lo;
-    amax = fmaxf(amax, fmaxf(fabsf(lo), fabsf(hi)));
-  }
-  const float emax = fmaxf(ext[0], fmaxf(ext[1], ext[2]));
-  float vol = 1.f;                           // degenerate sides lifted to 1/1024 of the longest one (planar / linear targets)
-  for (int k = 0; k < 3; ++k) vol *= fmaxf(ext[k], emax * (1.f / 1024.f));
-  float h = emax > 0.f ? cbrtf(vol * 8.f / (float)n) : 1.f;
-  h = fmaxf(h, emax * (1.f / 1024.f));
-  if (!(h > 0.f) || !isfinite(h)) h = 1.f;
-  for (int iter = 0; iter < 32; ++iter) {
-    long long cells = 1;
-    for (int k = 0; k < 3; ++k) { G.g[k] = min(1024, max(1, (int)floorf(ext[k] / h) + 1)); cells *= G.g[k]; }
-    if (cells <= (long long)mcells) break;
-    h *= 1.26f;
-  }
-  if ((long long)G.g[0] * G.g[1] * G.g[2] > (long long)mcells) G.g[0] = G.g[1] = G.g[2] = 1;   // non-finite extents: one cell
-  G.cells = G.g[0] * G.g[1] * G.g[2];
-  G.gmax = max(G.g[0], max(G.g[1], G.g[2]));
-  G.h = h; G.inv_h = 1.f / h;
-  G.eps = kCellSlack * (amax + emax) + 1e-30f;
-  G.n = n;
-  *out = G;
-}
-
-__global__ void __launch_bounds__(kThreads) nn_count_kernel(int n, const float* __restrict__ xyz, NnXform T, const NnGrid* __restrict__ Gp,
-                                                            uint32_t* __restrict__ count, uint32_t* __restrict__ cell_of) {
-  const int i = blockIdx.x * kThreads + threadIdx.x;
-  if (i >= n) return;
-  const NnGrid G = *Gp;
-  const F3 p = apply(T, ld3(xyz + 3 * (size_t)i));
-  const int cx = cell_coord(p.x, G.lo[0], G.inv_h, G.g[0]), cy = cell_coord(p.y, G.lo[1], G.inv_h, G.g[1]),
-            cz = cell_coord(p.z, G.lo[2], G.inv_h, G.g[2]);
-  const uint32_t c = (uint32_t)((cz * G.g[1] + cy) * G.g[0] + cx);
-  cell_of[i] = c;
-  atomicAdd(&count[c], 1u);
-}
-
-// exclusive scan of count[0..cells) by one 1024-thread workgroup
-__global__ void __launch_bounds__(1024) nn_scan_kernel(const NnGrid* __restrict__ Gp, const uint32_t* __restrict__ count,
-                                                       uint32_t* __restrict__ start, uint32_t* __restrict__ cursor) {
-  __shared__ uint32_t red[16];
-  const int cells = Gp->cells, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t carry = 0;
-  for (int base = 0; base < cells; base += 1024) {
-    const int i = base + (int)threadIdx.x;
-    const uint32_t v = i < cells ? count[i] : 0u;
-    const uint32_t inc = wave_scan_add_u32(v);
-    if (lane == 63) red[wv] = inc;
-    __syncthreads();
-    uint32_t pre = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) { const uint32_t r = red[w]; pre += w < wv ? r : 0u; tot += r; }
-    __syncthreads();
-    if (i < cells) { start[i] = carry + pre + inc - v; cursor[i] = carry + pre + inc - v; }
-    carry += tot;
-  }
-}
-
-__global__ void __launch_bounds__(kThreads) nn_fill_kernel(int n, const float* __restrict__ xyz, NnXform T, const uint32_t* __restrict__ cell_of,
-                                                           uint32_t* __restrict__ cursor, float* __restrict__ sxyz, uint32_t* __restrict__ sidx) {
-  const int i = blockIdx.x * kThreads + threadIdx.x;
-  if (i >= n) return;
-  const F3 p = apply(T, ld3(xyz + 3 * (size_t)i));
-  const uint32_t pos = atomicAdd(&cursor[cell_of[i]], 1u);      // order inside a cell is arbitrary: the query does not depend on it
-  sxyz[3 * pos] = p.x; sxyz[3 * pos + 1] = p.y; sxyz[3 * pos + 2] = p.z;
-  sidx[pos] = (uint32_t)i;
-}
-
+// ---- nearest-neighbour query over a point grid: outside queries, max_dist and index ties
 // squared distance from q to the box [a, b] (per axis)
 __device__ __forceinline__ float box_d2(const float q[3], const float a[3], const float b[3]) {
   float s = 0.f;
@@ -286,14 +156,14 @@ __device__ __forceinline__ float box_d2(const float q[3], const float a[3], cons
 // when every point outside the searched box is provably farther than the best (the distance from q to the part of the target's
 // bounding box beyond each open face, every box widened by eps for the rounding of cell coordinates), or, with max_dist, when
 // they are all beyond max_dist.  r <= gmax covers the whole grid.  Ties (equal fp32 squared distance) go to the smaller index.
-__global__ void __launch_bounds__(kThreads) nn_query_kernel(int nq, const float* __restrict__ query, NnXform T, float max_d2,
-                                                            const NnGrid* __restrict__ Gp, const uint32_t* __restrict__ start,
+__global__ void __launch_bounds__(kThreads) nn_query_kernel(int nq, const float* __restrict__ query, PointXform T, float max_d2,
+                                                            const PointGrid* __restrict__ Gp, const uint32_t* __restrict__ start,
                                                             const uint32_t* __restrict__ count, const float* __restrict__ sxyz,
                                                             const uint32_t* __restrict__ sidx, float* __restrict__ dist,
                                                             int32_t* __restrict__ idx) {
   const int t = blockIdx.x * kThreads + threadIdx.x;
   if (t >= nq) return;
-  const NnGrid G = *Gp;
+  const PointGrid G = *Gp;
   const F3 p = apply(T, ld3(query + 3 * (size_t)t));
   const float q[3] = {p.x, p.y, p.z};
   const float eps = G.eps + kCellSlack * fmaxf(fabsf(q[0]), fmaxf(fabsf(q[1]), fabsf(q[2])));
@@ -354,7 +224,7 @@ __global__ void __launch_bounds__(kThreads) nn_query_kernel(int nq, const float*
 }
 
 // ---- fixed-order reductions (wave_sum_f64, block_partials: sgr_common.h)
-__global__ void __launch_bounds__(kThreads) icp_partial_kernel(int n, const float* __restrict__ src, NnXform T, const int32_t* __restrict__ idx,
+__global__ void __launch_bounds__(kThreads) icp_partial_kernel(int n, const float* __restrict__ src, PointXform T, const int32_t* __restrict__ idx,
                                                                int nt, const float* __restrict__ tgt, double* __restrict__ parts) {
   double acc[kIcpSums];
 #pragma unroll
@@ -403,11 +273,6 @@ __global__ void __launch_bounds__(kThreads) reduce_final_kernel(int width, int g
 
 inline size_t sample_bytes(int F) { const size_t nb = (size_t)(F + kScanBlock - 1) / kScanBlock; return 2 * align_up((size_t)F * 8) + align_up((nb + 1) * 8); }
 
-inline NnXform xform(const float* m) {
-  NnXform T{};
-  if (m) { for (int k = 0; k < 12; ++k) T.m[k] = m[k]; T.on = 1; }
-  return T;
-}
 inline bool finite12(const float* m) {
   if (!m) return true;
   for (int k = 0; k < 12; ++k) if (!std::isfinite(m[k])) return false;
@@ -436,12 +301,12 @@ int sgr_surface_sample(int32_t V, int32_t F, const float* vertices, const int32_
   double* cdf = (double*)((char*)scratch + align_up((size_t)F * 8));
   double* sums = (double*)((char*)scratch + 2 * align_up((size_t)F * 8));
   const int nb = (F + kScanBlock - 1) / kScanBlock;
-  hipLaunchKernelGGL(area_kernel, dim3(blocks(F)), dim3(kThreads), 0, st, V, F, vertices, triangles, area, cdf);
+  hipLaunchKernelGGL(area_kernel, dim3(blocks_for(F)), dim3(kThreads), 0, st, V, F, vertices, triangles, area, cdf);
   hipLaunchKernelGGL(cdf_local_kernel, dim3(nb), dim3(kThreads), 0, st, F, cdf, sums);
   hipLaunchKernelGGL(cdf_sums_kernel, dim3(1), dim3(kThreads), 0, st, nb, sums);
-  hipLaunchKernelGGL(cdf_add_kernel, dim3(blocks(F)), dim3(kThreads), 0, st, F, cdf, sums);
+  hipLaunchKernelGGL(cdf_add_kernel, dim3(blocks_for(F)), dim3(kThreads), 0, st, F, cdf, sums);
   if (n > 0)
-    hipLaunchKernelGGL(sample_kernel, dim3(blocks(n)), dim3(kThreads), 0, st, n, V, F, vertices, triangles, area, cdf, seed, points,
+    hipLaunchKernelGGL(sample_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, n, V, F, vertices, triangles, area, cdf, seed, points,
                        tri_idx);
   if (total_area && hipMemcpyAsync(total_area, cdf + (F - 1), 8, hipMemcpyDeviceToDevice, st) != hipSuccess)
     return set_error(SGR_ERR_HIP, "surface_sample: copy");
@@ -450,38 +315,27 @@ int sgr_surface_sample(int32_t V, int32_t F, const float* vertices, const int32_
 
 size_t sgr_nn_grid_bytes(int32_t n) {
   if (n <= 0) return 0;
-  return blob_bytes(n);
+  return point_grid_bytes(n);
 }
 
 int sgr_nn_grid_build(int32_t n, const float* points, const float* transform, void* grid, size_t grid_bytes, void* stream) {
   if (n <= 0 || !points) return set_error(SGR_ERR_INVALID, "nn_grid_build: bad arguments (n=%d)", n);
-  if (!grid || grid_bytes < blob_bytes(n)) return set_error(SGR_ERR_WORKSPACE, "nn_grid_build: grid buffer too small");
+  if (!grid || grid_bytes < point_grid_bytes(n)) return set_error(SGR_ERR_WORKSPACE, "nn_grid_build: grid buffer too small");
   if (!finite12(transform)) return set_error(SGR_ERR_INVALID, "nn_grid_build: transform is not finite");
-  hipStream_t st = (hipStream_t)stream;
-  Blob b = carve(grid, n);
-  const NnXform T = xform(transform);
-  const size_t mc = max_cells(n);
-  if (hipMemsetAsync(b.mm, 0xff, 12, st) != hipSuccess || hipMemsetAsync(b.mm + 3, 0, 12, st) != hipSuccess ||
-      hipMemsetAsync(b.count, 0, mc * 4, st) != hipSuccess)
-    return set_error(SGR_ERR_HIP, "nn_grid_build: memset");
-  hipLaunchKernelGGL(nn_bounds_kernel, dim3(std::min(256, blocks(n))), dim3(kThreads), 0, st, n, points, T, b.mm);
-  hipLaunchKernelGGL(nn_setup_kernel, dim3(1), dim3(64), 0, st, n, (int)mc, b.mm, b.grid);
-  hipLaunchKernelGGL(nn_count_kernel, dim3(blocks(n)), dim3(kThreads), 0, st, n, points, T, b.grid, b.count, b.cell_of);
-  hipLaunchKernelGGL(nn_scan_kernel, dim3(1), dim3(1024), 0, st, b.grid, b.count, b.start, b.cursor);
-  hipLaunchKernelGGL(nn_fill_kernel, dim3(blocks(n)), dim3(kThreads), 0, st, n, points, T, b.cell_of, b.cursor, b.sxyz, b.sidx);
-  return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "nn_grid_build launch failed");
+  if (!build_point_grid(n, points, transform, grid, (hipStream_t)stream)) return set_error(SGR_ERR_HIP, "nn_grid_build: grid build failed");
+  return SGR_OK;
 }
 
 int sgr_nn_query(int32_t n, const void* grid, size_t grid_bytes, int32_t nq, const float* query, const float* transform, float max_dist,
                  float* dist, int32_t* idx, void* stream) {
   if (n <= 0 || nq < 0 || (nq > 0 && (!query || !dist || !idx)) || !(max_dist >= 0.f))
     return set_error(SGR_ERR_INVALID, "nn_query: bad arguments (n=%d nq=%d)", n, nq);
-  if (!grid || grid_bytes < blob_bytes(n)) return set_error(SGR_ERR_WORKSPACE, "nn_query: grid buffer too small");
+  if (!grid || grid_bytes < point_grid_bytes(n)) return set_error(SGR_ERR_WORKSPACE, "nn_query: grid buffer too small");
   if (!finite12(transform)) return set_error(SGR_ERR_INVALID, "nn_query: transform is not finite");
   if (nq == 0) return SGR_OK;
-  Blob b = carve((void*)grid, n);
+  const GridBlob b = carve_grid((void*)grid, n);
   const float max_d2 = std::isinf(max_dist) ? INFINITY : max_dist * max_dist;
-  hipLaunchKernelGGL(nn_query_kernel, dim3(blocks(nq)), dim3(kThreads), 0, (hipStream_t)stream, nq, query, xform(transform), max_d2,
+  hipLaunchKernelGGL(nn_query_kernel, dim3(blocks_for(nq)), dim3(kThreads), 0, (hipStream_t)stream, nq, query, point_xform(transform), max_d2,
                      b.grid, b.start, b.count, b.sxyz, b.sidx, dist, idx);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "nn_query launch failed");
 }
@@ -496,7 +350,7 @@ int sgr_icp_accumulate(int32_t n, const float* source, const float* transform, c
   if (!finite12(transform)) return set_error(SGR_ERR_INVALID, "icp_accumulate: transform is not finite");
   hipStream_t st = (hipStream_t)stream;
   double* parts = (double*)scratch;
-  hipLaunchKernelGGL(icp_partial_kernel, dim3(kRedBlocks), dim3(kThreads), 0, st, n, source, xform(transform), idx, n_target, target, parts);
+  hipLaunchKernelGGL(icp_partial_kernel, dim3(kRedBlocks), dim3(kThreads), 0, st, n, source, point_xform(transform), idx, n_target, target, parts);
   hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kThreads), 0, st, kIcpSums, 1, parts, sums);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "icp_accumulate launch failed");
 }

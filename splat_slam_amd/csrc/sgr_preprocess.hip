@@ -10,6 +10,7 @@
 // registers) -- HBM bytes, not flops, bound these kernels.  Per-Gaussian pose gradients are reduced in-kernel
 // (wave DPP + LDS) to one 6-vector per block, then by a fixed-order second stage: deterministic, no [N,6] buffer.
 #include "sgr_common.h"
+#include "sgr_scan.h"
 #include "sgr_adam_device.h"
 
 namespace sgr {

@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "sgr_common.h"
+#include "sgr_scan.h"
 #include "sgr_se3_device.h"
 
 namespace sgr {
@@ -28,8 +29,7 @@ constexpr int kWide = 1024, kWideWaves = kWide / 64;       // launch 2: one work
 constexpr int kPartRow = 8;                                // doubles per workgroup partial (7 of accumulate, 5 of errors)
 constexpr int kFitSums = 7, kCentredSums = 10, kErrSums = 3;
 
-inline int blocks(int n) { return (n + kThreads - 1) / kThreads; }
-inline size_t parts_bytes(int n) { return align_up((size_t)blocks(n) * kPartRow * 8); }
+inline size_t parts_bytes(int n) { return align_up((size_t)blocks_for(n) * kPartRow * 8); }
 inline size_t total_bytes(int n) { return parts_bytes(n) + align_up((size_t)n * 8); }
 
 struct Sim3 { double s, r[9], t[3]; };
@@ -275,10 +275,10 @@ __global__ void __launch_bounds__(kWide) traj_item_stats_kernel(int n, int nb, c
 }
 
 // ---- sgr_traj_associate ------------------------------------------------------------------------------------------------------------
-constexpr int kOrderBlocksMax = 1024;      // launch 1 has at least blocks(na) workgroups and up to this many for the order check of b
+constexpr int kOrderBlocksMax = 1024;      // launch 1 has at least blocks_for(na) workgroups and up to this many for the order check of b
 inline int assoc_blocks(int na, int nb) {
-  const int order = blocks(nb) < kOrderBlocksMax ? blocks(nb) : kOrderBlocksMax;
-  return blocks(na) > order ? blocks(na) : order;
+  const int order = blocks_for(nb) < kOrderBlocksMax ? blocks_for(nb) : kOrderBlocksMax;
+  return blocks_for(na) > order ? blocks_for(na) : order;
 }
 
 // launch 1: thread i < na searches a[i]; ALL threads of the grid stride over j < nb - 1 for the order check.  flags[block] = 1 iff the
@@ -313,20 +313,6 @@ __global__ void __launch_bounds__(kThreads) traj_associate_kernel(int na, const 
   if (threadIdx.x == 0) flags[blockIdx.x] = s_bad[0] | s_bad[1] | s_bad[2] | s_bad[3];
 }
 
-// exclusive prefix of `v` inside a 1024-thread workgroup + its total; red: 16 uints of LDS
-__device__ __forceinline__ uint32_t block1024_exclusive_scan(uint32_t v, uint32_t* red, uint32_t& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const uint32_t inc = wave_scan_add_u32(v);
-  if (lane == 63) red[wv] = inc;
-  __syncthreads();
-  uint32_t base = 0u, sum = 0u;
-#pragma unroll
-  for (int w = 0; w < kWideWaves; ++w) { base += w < wv ? red[w] : 0u; sum += red[w]; }
-  __syncthreads();
-  total = sum;
-  return base + inc - v;
-}
-
 // launch 2, one workgroup: the flags of the workgroups, the compacted lists in the order of i, the header
 __global__ void __launch_bounds__(kWide) traj_compact_kernel(int na, int nflags, const int32_t* __restrict__ match, const int32_t* __restrict__ flags,
                                                              int32_t* __restrict__ a_inds, int32_t* __restrict__ b_inds,
@@ -344,7 +330,7 @@ __global__ void __launch_bounds__(kWide) traj_compact_kernel(int na, int nflags,
     const int i = i0 + tid;
     const int j = i < na ? match[i] : -1;
     uint32_t total;
-    const uint32_t r = base + block1024_exclusive_scan(j >= 0 ? 1u : 0u, s_red, total);
+    const uint32_t r = base + block_exclusive_scan<kWideWaves>(j >= 0 ? 1u : 0u, s_red, total);
     if (j >= 0) { a_inds[r] = i; b_inds[r] = j; }
     base += total;
   }
@@ -529,7 +515,7 @@ inline bool supported(int n) { return n >= 1 && n <= SGR_TRAJ_MAX_POSES; }
 inline size_t assoc_bytes(int na, int nb) { return align_up((size_t)assoc_blocks(na, nb) * 4); }
 // parts | counts | used | rank_row | mats
 inline size_t pe_counts_off(int n) { return parts_bytes(n); }
-inline size_t pe_used_off(int n) { return pe_counts_off(n) + align_up((size_t)blocks(n) * 4); }
+inline size_t pe_used_off(int n) { return pe_counts_off(n) + align_up((size_t)blocks_for(n) * 4); }
 inline size_t pe_rank_off(int n) { return pe_used_off(n) + align_up((size_t)n); }
 inline size_t pe_mats_off(int n) { return pe_rank_off(n) + align_up((size_t)n * 4); }
 inline size_t pe_bytes(int n) { return pe_mats_off(n) + align_up((size_t)n * kMatDoubles * 8); }
@@ -562,7 +548,7 @@ int sgr_traj_accumulate(int32_t kind, const float* est, int32_t est_rows, const 
     if (hipMemcpyAsync(rows, inds, (size_t)n * 8, hipMemcpyHostToDevice, st) != hipSuccess)
       return set_error(SGR_ERR_HIP, "traj_accumulate: copy of inds");
   }
-  const int nb = blocks(n);
+  const int nb = blocks_for(n);
   if (kind == SGR_TRAJ_POSE7_W2C)
     hipLaunchKernelGGL(traj_centres_kernel<SGR_TRAJ_POSE7_W2C>, dim3(nb), dim3(kThreads), 0, st, n, est, rows, ref, pos, valid, parts);
   else
@@ -581,7 +567,7 @@ int sgr_traj_errors(int32_t n, const double* pos, const uint8_t* valid, const do
   for (int k = 0; k < 3; ++k) T.t[k] = sim3[10 + k];
   hipStream_t st = (hipStream_t)stream;
   double* parts = (double*)scratch;
-  const int nb = blocks(n);
+  const int nb = blocks_for(n);
   hipLaunchKernelGGL(traj_errors_kernel, dim3(nb), dim3(kThreads), 0, st, n, pos, valid, T, err, parts);
   hipLaunchKernelGGL(traj_stats_kernel, dim3(1), dim3(kWide), 0, st, n, nb, err, valid, parts, stats);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "traj_errors launch failed");
@@ -631,7 +617,7 @@ int sgr_traj_pose_errors(int32_t kind, const float* est, int32_t est_rows, const
   uint8_t* used = (uint8_t*)(base + pe_used_off(n));
   int32_t* rank_row = (int32_t*)(base + pe_rank_off(n));
   double* mats = (double*)(base + pe_mats_off(n));
-  const int nb = blocks(n);
+  const int nb = blocks_for(n);
   if (kind == SGR_TRAJ_POSE7_W2C)
     hipLaunchKernelGGL(traj_poses_kernel<SGR_TRAJ_POSE7_W2C>, dim3(nb), dim3(kThreads), 0, st, n, est, est_rows, ref, ref_rows, est_inds,
                        ref_inds, T, mats, used, counts);

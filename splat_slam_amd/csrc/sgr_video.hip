@@ -28,8 +28,6 @@ constexpr int kSub = 8;                     // upsampling factor: 8 x 8 outputs 
 constexpr int kMaskChannels = 9 * kSub * kSub;
 constexpr int kMaxNum = SGR_VIDEO_MAX_FRAMES;      // frames per call (a grid dimension, and the limit of sgr_dba_depth_filter)
 
-inline int blocks(long long n, int per = kThreads) { return (int)((n + per - 1) / per); }
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ================================================================================================================================
 // convex upsampling.  One thread per (coarse pixel p, sub-row dy): its 9 x 8 logits are 72 independent loads, each of them one
@@ -284,7 +282,7 @@ size_t carve(int num, int P, char* base, VideoScratch* s) {
   size_t off = 0;
   auto take = [&](size_t bytes) {
     char* p = base ? base + off : nullptr;
-    off += align256(bytes);
+    off += align_up(bytes);
     return p;
   };
   VideoScratch d;
@@ -309,15 +307,15 @@ int launch_mask(const float* disps, int nf, int P, const int64_t* inds, int num,
                 const VideoScratch& s, hipStream_t st) {
   const float vis = (float)visible_num;
   const size_t words = (size_t)num * kPasses * kBins;
-  const dim3 hg(blocks(P, kHistPixels), num);
-  hipLaunchKernelGGL(zero_kernel, dim3(blocks((long long)words)), dim3(kThreads), 0, st, s.hist, words);
+  const dim3 hg(blocks_for(P, kHistPixels), num);
+  hipLaunchKernelGGL(zero_kernel, dim3(blocks_for((long long)words)), dim3(kThreads), 0, st, s.hist, words);
   hipLaunchKernelGGL(hist_kernel<0>, hg, dim3(kThreads), 0, st, nf, P, disps, inds, counts, vis, s.state, s.hist);
   hipLaunchKernelGGL(select_kernel<0>, dim3(num), dim3(kThreads), 0, st, nf, inds, s.hist, s.state);
   hipLaunchKernelGGL(hist_kernel<1>, hg, dim3(kThreads), 0, st, nf, P, disps, inds, counts, vis, s.state, s.hist);
   hipLaunchKernelGGL(select_kernel<1>, dim3(num), dim3(kThreads), 0, st, nf, inds, s.hist, s.state);
   hipLaunchKernelGGL(hist_kernel<2>, hg, dim3(kThreads), 0, st, nf, P, disps, inds, counts, vis, s.state, s.hist);
   hipLaunchKernelGGL(select_kernel<2>, dim3(num), dim3(kThreads), 0, st, nf, inds, s.hist, s.state);
-  hipLaunchKernelGGL(mask_kernel, dim3(blocks(P), num), dim3(kThreads), 0, st, nf, P, disps, inds, counts, vis, s.state, mask_out);
+  hipLaunchKernelGGL(mask_kernel, dim3(blocks_for(P), num), dim3(kThreads), 0, st, nf, P, disps, inds, counts, vis, s.state, mask_out);
   return hipGetLastError() == hipSuccess ? SGR_OK : set_error(SGR_ERR_HIP, "video_mask_from_counts launch failed");
 }
 
@@ -335,7 +333,7 @@ int sgr_video_cvx_upsample(const float* disps, int32_t num_frames, int32_t ht, i
       ((uintptr_t)disps_up & 15) != 0)
     return set_error(SGR_ERR_INVALID, "video_cvx_upsample: bad arguments (disps_up must be 16-byte aligned, num <= %d)", kMaxNum);
   if (num == 0) return SGR_OK;
-  const dim3 grid(blocks((long long)ht * wd, 64), 2, num);
+  const dim3 grid(blocks_for((long long)ht * wd, 64), 2, num);
   if (mask_kind == SGR_VIDEO_MASK_F32)
     hipLaunchKernelGGL(cvx_upsample_kernel<float>, grid, dim3(kThreads), 0, (hipStream_t)stream, num_frames, ht, wd, disps, inds,
                        (const float*)mask, disps_up);

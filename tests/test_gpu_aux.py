@@ -64,6 +64,60 @@ def test_knn_grid_path_is_exact(shape):
     assert torch.allclose(got, ref, rtol=2e-5, atol=1e-9), float((got - ref).abs().max())
 
 
+def test_knn_is_the_same_on_both_sides_of_the_brute_to_grid_switch():
+    """16383 points go through all pairs, 16384 through the point grid (csrc/sgr_point_grid.hip).  The same first 16383 points, with a
+    duplicate among them, in both runs: each run is exact, and a point's mean changes between the runs only where the added point
+    is among its three nearest.  Which points those are is decided in fp64 with a relative margin of 1e-5 on the squared distances:
+    the inputs are fp32 values, so fp64 forms the distances almost exactly, and fp32 forms them to a few 2^-24 (6e-8 each for the
+    three differences, squares and two sums), far inside the margin.  Points inside the margin may go either way."""
+    from simple_knn._C import distCUDA2
+    n = 16384
+    pts = torch.randn(n, 3, generator=torch.Generator().manual_seed(5)) * torch.tensor([3.0, 1.0, 0.2])
+    pts[7] = pts[3]                                             # a duplicate: distance 0 is a legal neighbour
+    pts[n - 1] = pts[100] + torch.tensor([0.01, -0.02, 0.005])  # the added point sits inside the cloud: it has neighbours
+    brute = distCUDA2(pts[:n - 1].contiguous().to(DEV)).cpu()
+    grid = distCUDA2(pts.to(DEV)).cpu()
+    ref_brute, ref_grid = _knn_ref_chunked(pts[:n - 1]), _knn_ref_chunked(pts)
+    assert torch.allclose(brute.double(), ref_brute, rtol=2e-5, atol=1e-9), float((brute.double() - ref_brute).abs().max())
+    assert torch.allclose(grid.double(), ref_grid, rtol=2e-5, atol=1e-9), float((grid.double() - ref_grid).abs().max())
+    x, added = pts[:n - 1].double(), pts[n - 1].double()
+    d_added = ((x - added) ** 2).sum(1)
+    third = torch.empty(n - 1, dtype=torch.float64)             # third-nearest squared distance among the first 16383
+    for a in range(0, n - 1, 500):
+        d2 = torch.cdist(x[a:a + 500], x) ** 2
+        d2[torch.arange(d2.shape[0]), torch.arange(a, a + d2.shape[0])] = float("inf")
+        third[a:a + 500] = torch.topk(d2, 3, dim=1, largest=False).values[:, 2]
+    surely, maybe = d_added < third * (1 - 1e-5), d_added <= third * (1 + 1e-5)
+    differs = brute != grid[:n - 1]
+    print("points whose mean the added point changes: %d surely, %d possibly, %d differ" % (int(surely.sum()), int(maybe.sum()), int(differs.sum())))
+    assert int(surely.sum()) >= 3                               # the added point is somebody's neighbour
+    assert bool((differs <= maybe).all()), int((differs & ~maybe).sum())
+    assert bool((grid[:n - 1][surely] < brute[surely]).all())
+
+
+@pytest.mark.parametrize("mask", ["all", "none", "third"])
+@pytest.mark.parametrize("n", [0, 1, 255, 256, 257, 262144, 262145])
+def test_keep_list_equals_torch_nonzero(n, mask):
+    """sgr_keep_list: a 256-row block scan, the scan of the block totals by one workgroup in chunks of 1024, an ordered second pass.
+    262144 rows are exactly 1024 block totals (one full chunk), 262145 rows are 1025 (the carry into a second chunk)."""
+    from splat_slam_amd import _native as nat
+    lib = nat.lib()
+    if mask == "third":
+        keep = torch.rand(n, generator=torch.Generator().manual_seed(n + 1)) < 1.0 / 3.0
+    else:
+        keep = torch.full((n,), mask == "all", dtype=torch.bool)
+    want = torch.nonzero(keep).flatten().to(torch.int32)
+    k8 = keep.to(torch.uint8).to(DEV)
+    src = torch.full((max(n, 1),), -7, dtype=torch.int32, device=DEV)
+    cnt = torch.full((1,), -1, dtype=torch.int64, device=DEV)
+    scratch = torch.empty(lib.sgr_compact_scratch_bytes(n), dtype=torch.uint8, device=DEV)
+    nat.check(lib.sgr_keep_list(n, k8.data_ptr(), src.data_ptr(), cnt.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                torch.cuda.current_stream().cuda_stream), "sgr_keep_list")
+    assert int(cnt.item()) == want.numel()
+    assert torch.equal(src[:want.numel()].cpu(), want)
+    assert bool((src[want.numel():] == -7).all())               # nothing is written past the list
+
+
 def test_se3_ops_match_oracle_and_reference_exp():
     import lietorch
     from oracle import aux_oracle as A

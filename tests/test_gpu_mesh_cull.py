@@ -231,8 +231,44 @@ def test_selection_that_keeps_everything_and_nothing():
     assert len(out) == 0 and out.triangles.shape[0] == 0 and bool((vmap == -1).all())
 
 
+@pytest.mark.parametrize("V,F", [(0, 0), (1, 1), (4096, 4095), (4097, 4097)])
+def test_selection_of_every_second_face_at_the_scan_block_edges(V, F):
+    """sgr_cull_select + sgr_cull_compact straight on the C ABI (mesh_cull.select refuses a mesh without vertices) around the 4096-item
+    block of the device-wide scan that the culling shares with the mesh cleaning: an empty mesh, one face, one item short of a block
+    and one past it.  Face f joins vertices of its own parity (f, f - 2, f - 4; no wrap), and only even vertices were seen, so under
+    either rule exactly the faces 0, 2, 4, ... stay, with the even vertices."""
+    from splat_slam_amd import _native as nat
+    from splat_slam_amd.mesh_cull import RULES
+    lib = nat.lib()
+    f = np.arange(F, dtype=np.int64)
+    t = np.stack([f, np.where(f >= 2, f - 2, f), np.where(f >= 4, f - 4, f)], 1).astype(np.int32).reshape(F, 3)
+    seen = (np.arange(V) % 2 == 0).astype(np.int32)
+    rng = np.random.default_rng(V + 1)
+    v, c = rng.standard_normal((V, 3)).astype(np.float32), rng.random((V, 3)).astype(np.float32)
+    kv, kf, faces, want_map = ref.select(V, t, seen, 1, "all")
+    assert np.array_equal(kf, np.arange(0, F, 2)) and np.array_equal(kv, np.arange(0, V, 2))
+    dv, dc, dt, ds = (torch.from_numpy(a).to(DEV) for a in (v, c, t, seen))
+    st = torch.cuda.current_stream().cuda_stream
+    for rule in ("all", "any"):
+        nbytes = lib.sgr_cull_select_bytes(V, F)
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+        totals = torch.full((2,), -1, dtype=torch.int32, device=DEV)
+        nat.check(lib.sgr_cull_select(V, F, dt.data_ptr(), ds.data_ptr(), 1, RULES[rule], scratch.data_ptr(), nbytes, totals.data_ptr(), st),
+                  "sgr_cull_select")
+        assert totals.tolist() == [len(kv), len(kf)], rule
+        ov = torch.empty(len(kv), 3, dtype=torch.float32, device=DEV)
+        oc = torch.empty(len(kv), 3, dtype=torch.float32, device=DEV)
+        ot = torch.empty(len(kf), 3, dtype=torch.int32, device=DEV)
+        vmap = torch.full((V,), -5, dtype=torch.int32, device=DEV)
+        nat.check(lib.sgr_cull_compact(V, F, dv.data_ptr(), dc.data_ptr(), dt.data_ptr(), scratch.data_ptr(), nbytes, ov.data_ptr(),
+                                       oc.data_ptr(), ot.data_ptr(), vmap.data_ptr(), st), "sgr_cull_compact")
+        assert np.array_equal(_np(vmap), want_map), rule
+        assert np.array_equal(_np(ot), faces.reshape(-1, 3)), rule
+        assert np.array_equal(_np(ov), v[kv]) and np.array_equal(_np(oc), c[kv]), rule
+
+
 # ---- end to end
-SCALE = 5                       # 240 x 320 images
+SCALE = 5                      # 240 x 320 images
 
 
 @pytest.fixture(scope="module")

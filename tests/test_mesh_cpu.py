@@ -1,6 +1,6 @@
 """The TSDF mesh without a GPU: the generated marching-cubes table (csrc/sgr_mc_table.h) is what scripts/gen_mc_table.py writes
 and cannot crack, the fp64 restatement (tests/mesh_ref.py) fuses an analytic sphere into one closed genus-0 surface,
-csrc/sgr_mesh.hip compiles for gfx950 without scratch, spills or float atomics, splat_slam_amd.mesh refuses what it does not
+csrc/sgr_mesh.hip (with the shared csrc/sgr_scan.hip) compiles for gfx950 without scratch, spills or float atomics, splat_slam_amd.mesh refuses what it does not
 implement, and the cases of tests/mesh_cases.py meet, on the restatement alone, the conditions that make them worth running on
 the kernels (tests/test_gpu_mesh_edges.py)."""
 import os
@@ -17,8 +17,10 @@ import mesh_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-KERNELS = ("tsdf_touch_kernel", "tsdf_list_kernel", "tsdf_rehash_kernel", "tsdf_integrate_kernel", "scan_blocks_kernel",
-           "scan_sums_kernel", "scan_add_kernel", "gather_units_kernel", "bitonic_step_kernel", "mc_count_kernel", "mc_emit_kernel",
+# the file and what it launches through sgr_scan.h (the scans, the compaction)
+SOURCES = ("sgr_mesh", "sgr_scan")
+KERNELS = ("tsdf_touch_kernel", "tsdf_list_kernel", "tsdf_rehash_kernel", "tsdf_integrate_kernel", "scan_local_kernel",
+           "chunked_scan_kernel", "scan_add_kernel", "gather_units_kernel", "bitonic_step_kernel", "mc_count_kernel", "mc_emit_kernel",
            "cc_init_kernel", "cc_union_kernel", "cc_flatten_kernel", "cc_keep_vertices_kernel", "tri_keep_kernel",
            "tri_bucket_kernel", "tri_dedup_kernel", "compact_vertices_kernel", "compact_triangles_kernel")
 
@@ -142,15 +144,18 @@ def test_restated_cleaning_drops_small_components():
 def mesh_isa(tmp_path_factory):
     if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
         pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa") / "mesh.s")
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-S", "--cuda-device-only", "-o", out,
-                    os.path.join(ROOT, "splat_slam_amd", "csrc", "sgr_mesh.hip")], check=True, capture_output=True)
-    text = open(out).read()
-    meta = {}
-    for block in text.split("\n  - ")[1:]:
-        m = re.search(r"\.name:\s+(\S+)", block)
-        if m and ".private_segment_fixed_size" in block:
-            meta[m.group(1)] = block
+    text, meta = "", {}
+    for src in SOURCES:
+        out = str(tmp_path_factory.mktemp("isa") / (src + ".s"))
+        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-S", "--cuda-device-only", "-o", out,
+                        os.path.join(ROOT, "splat_slam_amd", "csrc", src + ".hip")], check=True, capture_output=True)
+        one = open(out).read()
+        text += one
+        for block in one.split("\n  - ")[1:]:
+            m = re.search(r"\.name:\s+(\S+)", block)
+            if m and ".private_segment_fixed_size" in block:
+                assert m.group(1) not in meta, m.group(1)
+                meta[m.group(1)] = block
     return text, meta
 
 

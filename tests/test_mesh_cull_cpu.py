@@ -1,4 +1,4 @@
-"""Mesh culling without a GPU: csrc/sgr_mesh_cull.hip compiles for gfx950 without scratch, spills or float atomics, its entry points
+"""Mesh culling without a GPU: csrc/sgr_mesh_cull.hip (with the shared csrc/sgr_scan.hip) compiles for gfx950 without scratch, spills or float atomics, its entry points
 are declared, exported and bound and refuse bad arguments before any launch, splat_slam_amd.mesh_cull refuses what it does not
 implement, the restatement of tests/mesh_cull_ref.py gets simple cases right, and the inputs of the GPU tests are well conditioned:
 no projected coordinate sits on a rounding tie."""
@@ -18,8 +18,9 @@ import mesh_cull_ref as ref
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 KERNELS = ("cull_project_kernel", "cull_raster_small_kernel", "cull_raster_large_kernel", "cull_visibility_kernel",
-           "cull_face_keep_kernel", "cull_scan_local_kernel", "cull_scan_sums_kernel", "cull_scan_add_kernel",
-           "cull_compact_vertices_kernel", "cull_compact_triangles_kernel")
+           "cull_face_keep_kernel", "scan_local_kernel", "chunked_scan_kernel", "scan_add_kernel",
+           "compact_vertices_kernel", "compact_triangles_kernel")
+SOURCES = ("sgr_mesh_cull", "sgr_scan")          # the file and what it launches through sgr_scan.h (the scans, the compaction)
 ENTRY_POINTS = ("sgr_cull_project", "sgr_cull_raster_bytes", "sgr_cull_raster", "sgr_cull_visibility", "sgr_cull_select_bytes",
                 "sgr_cull_select", "sgr_cull_compact")
 
@@ -29,15 +30,18 @@ ENTRY_POINTS = ("sgr_cull_project", "sgr_cull_raster_bytes", "sgr_cull_raster", 
 def cull_isa(tmp_path_factory):
     if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
         pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa") / "mesh_cull.s")
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-S", "--cuda-device-only", "-o", out,
-                    os.path.join(ROOT, "splat_slam_amd", "csrc", "sgr_mesh_cull.hip")], check=True, capture_output=True)
-    text = open(out).read()
-    meta = {}
-    for block in text.split("\n  - ")[1:]:
-        m = re.search(r"\.name:\s+(\S+)", block)
-        if m and ".private_segment_fixed_size" in block:
-            meta[m.group(1)] = block
+    text, meta = "", {}
+    for src in SOURCES:
+        out = str(tmp_path_factory.mktemp("isa") / (src + ".s"))
+        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-S", "--cuda-device-only", "-o", out,
+                        os.path.join(ROOT, "splat_slam_amd", "csrc", src + ".hip")], check=True, capture_output=True)
+        one = open(out).read()
+        text += one
+        for block in one.split("\n  - ")[1:]:
+            m = re.search(r"\.name:\s+(\S+)", block)
+            if m and ".private_segment_fixed_size" in block:
+                assert m.group(1) not in meta, m.group(1)
+                meta[m.group(1)] = block
     return text, meta
 
 

@@ -1,4 +1,4 @@
-"""Mesh evaluation without a GPU: csrc/sgr_mesh_eval.hip compiles for gfx950 without scratch, spills or float atomics, its entry
+"""Mesh evaluation without a GPU: csrc/sgr_mesh_eval.hip (with the shared csrc/sgr_point_grid.hip and csrc/sgr_scan.hip) compiles for gfx950 without scratch, spills or float atomics, its entry
 points are declared, exported and bound, read_mesh_ply reads the PLY variants ground-truth meshes come in, splat_slam_amd.mesh_eval
 refuses what it does not implement, and the fp64 restatement of tests/mesh_eval_ref.py gets simple cases right."""
 import ctypes
@@ -17,9 +17,12 @@ import mesh_eval_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-KERNELS = ("area_kernel", "cdf_local_kernel", "cdf_sums_kernel", "cdf_add_kernel", "sample_kernel", "nn_bounds_kernel",
-           "nn_setup_kernel", "nn_count_kernel", "nn_scan_kernel", "nn_fill_kernel", "nn_query_kernel", "icp_partial_kernel",
-           "metrics_partial_kernel", "reduce_final_kernel")
+# the file, the grid build it launches through sgr_point_grid.h, and that build's scan (sgr_scan.hip, with its other kernels)
+SOURCES = ("sgr_mesh_eval", "sgr_point_grid", "sgr_scan")
+KERNELS = ("area_kernel", "cdf_local_kernel", "cdf_sums_kernel", "cdf_add_kernel", "sample_kernel", "grid_bounds_kernel",
+           "grid_setup_kernel", "grid_count_kernel", "chunked_scan_kernel", "grid_fill_kernel", "nn_query_kernel", "icp_partial_kernel",
+           "metrics_partial_kernel", "reduce_final_kernel", "scan_local_kernel", "scan_add_kernel", "compact_vertices_kernel",
+           "compact_triangles_kernel")
 ENTRY_POINTS = ("sgr_surface_sample_bytes", "sgr_surface_sample", "sgr_nn_grid_bytes", "sgr_nn_grid_build", "sgr_nn_query",
                 "sgr_eval_reduce_bytes", "sgr_icp_accumulate", "sgr_cloud_metrics")
 
@@ -29,15 +32,18 @@ ENTRY_POINTS = ("sgr_surface_sample_bytes", "sgr_surface_sample", "sgr_nn_grid_b
 def eval_isa(tmp_path_factory):
     if not (os.path.exists(HIPCC) or shutil.which(HIPCC)):
         pytest.skip("hipcc not available")
-    out = str(tmp_path_factory.mktemp("isa") / "mesh_eval.s")
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-S", "--cuda-device-only", "-o", out,
-                    os.path.join(ROOT, "splat_slam_amd", "csrc", "sgr_mesh_eval.hip")], check=True, capture_output=True)
-    text = open(out).read()
-    meta = {}
-    for block in text.split("\n  - ")[1:]:
-        m = re.search(r"\.name:\s+(\S+)", block)
-        if m and ".private_segment_fixed_size" in block:
-            meta[m.group(1)] = block
+    text, meta = "", {}
+    for src in SOURCES:
+        out = str(tmp_path_factory.mktemp("isa") / (src + ".s"))
+        subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-S", "--cuda-device-only", "-o", out,
+                        os.path.join(ROOT, "splat_slam_amd", "csrc", src + ".hip")], check=True, capture_output=True)
+        one = open(out).read()
+        text += one
+        for block in one.split("\n  - ")[1:]:
+            m = re.search(r"\.name:\s+(\S+)", block)
+            if m and ".private_segment_fixed_size" in block:
+                assert m.group(1) not in meta, m.group(1)
+                meta[m.group(1)] = block
     return text, meta
 
 
